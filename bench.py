@@ -15,10 +15,17 @@ rendezvous on 127.0.0.1, one GPU each), forwards rank 0's line and exits with th
 `python bench.py --gpus 8` and the torch.distributed.run form above measure the same N-rank job (trainers/evaluate.py:170-179:
 the reference leaves the launch to Lightning's DDP strategy).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the gemm_nt tile variant with the largest time share; fp32-exact MFMA
-implicit GEMM): algorithmic FLOPs of its launches / their HIP-event durations, taken on the launch stream during
-extra steps that run AFTER the timed region (the timed steps carry no instrumentation).  `cpu_baseline` is the oracle (a CPU port validated against the
-reference) timed on this box's host cores on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the `--steps` steps, writes `--dump-outputs` if asked
+and prints that line (`roofline: null`).  `--full` adds what needs runs of its own: `roofline` for the dominant kernel (the gemm_nt
+tile variant with the largest time share; fp32-exact MFMA implicit GEMM): algorithmic FLOPs of its launches / their HIP-event
+durations, taken on the launch stream during extra steps that run AFTER the timed region (the timed steps carry no
+instrumentation), and `cpu_baseline`, the oracle (a CPU port validated against the reference) timed on this box's host cores on a
+bounded sample.  `loss` is that of the last step the run took: the last timed step in a plain run, the last profiled step with
+`--full`.
+
+`--dump-outputs DIR` writes what the last timed step computed (the loss, every quantity the step leaves in `model.last`, a fixed
+seeded sample of the updated parameters, gradients, Adam moments and EMA teacher) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -61,7 +68,11 @@ def parse():
     ap.add_argument("--classes", type=int, default=286)
     ap.add_argument("--variant", choices=["dvm", "saint", "cardiac", "mmatch", "comatch", "simmatch", "freematch"], default="dvm",
                     help="dvm = BASELINE configs[1..2] (the bench line); saint = config 4; cardiac = config 5 (26 cat + 49 con, K=2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what needs runs of its own: the roofline of the dominant kernel "
+                    "(extra profiled steps after the timed region) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64; larger tensors as a fixed seeded sample; at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=32, help="batch of the CPU baseline (BASELINE.md section 3: 32; 256 = the bench's own batch, ~2 min per step)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps after one warm-up (BASELINE.md section 3: >= 3)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (driver.GraphedTrainStep)")
@@ -304,6 +315,45 @@ def cpu_baseline(field_lengths, classes, img, batch, steps=3):
                 s_per_step=round(dt, 3))
 
 
+DUMP_SAMPLE = 1 << 18          # elements kept of a larger output (fixed seeded sample)
+DUMP_LIMIT = 64 << 20          # bytes written by --dump-outputs in all
+
+
+def _dump_array(t):
+    """-> numpy float32 (float64 for float64 / integer / bool tensors), a fixed seeded sample of at most DUMP_SAMPLE elements."""
+    t = t.detach()
+    t = t.reshape(-1) if t.numel() > DUMP_SAMPLE else t
+    if t.numel() > DUMP_SAMPLE:   # the same indices for the same size, whatever else is dumped
+        idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        t = t[idx.to(t.device)]
+    t = t.cpu()
+    keep64 = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+    return t.to(torch.float64 if keep64 else torch.float32).numpy()
+
+
+def dump_outputs(out_dir, m):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, as a caller of the step receives it -- the loss and
+    every tensor of `model.last`, and the updated flat state (parameters, gradients, Adam moments, EMA teacher) -- as
+    DIR/<name>.npy.  Returns the number of bytes written."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {}
+    for k, v in m.last.items():
+        if isinstance(v, torch.Tensor):
+            arrays[k] = _dump_array(v)
+        elif isinstance(v, (bool, int, float)):
+            arrays[k] = np.asarray(v, dtype=np.float64)
+    fl = m.flat
+    for k, v in (("params", fl.params), ("grads", fl._grads), ("exp_avg", fl.exp_avg), ("exp_avg_sq", fl.exp_avg_sq), ("ema", fl.ema)):
+        arrays["flat_" + k] = _dump_array(v)
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return total
+
+
 def main():
     a = parse()
     if a.precision == "bf16x3":      # before anything imports the operator layer (and inherited by the rank processes)
@@ -389,13 +439,15 @@ def main():
     dt = time.perf_counter() - t0
     per_rank = gather_times(torch.tensor([dt], dtype=torch.float64, device=dev), world)
     dt = max(per_rank)            # the contract: MAX over ranks
-    # OUTSIDE the timed region, two more steps.  (1) the step as timed (both streams), HIP events around the GEMM launches on
+    if a.dump_outputs and rank == 0:   # before anything below runs another step
+        dump_outputs(a.dump_outputs, m)
+    # --full (or --breakdown): OUTSIDE the timed region, two more steps.  (1) the step as timed (both streams), HIP events around the GEMM launches on
     # whichever stream they go to: the kernel while the side stream co-runs (`two_stream`).  (2) every launch kept on ONE
     # stream and bracketed by HIP events: clean per-kernel durations (no second kernel sharing the chip), which is what
     # the roofline of the kernel is priced on.
     # Ranks that share a device (gloo on the one-GPU test box) skip both: an event pair then also spans the OTHER process's
     # time slices, so it prices nothing (`roofline: null` with the reason).
-    if not shared_device:
+    if (a.full or a.breakdown) and not shared_device:
         if not a.graph:
             L.begin_profile(single_stream=False, only=("gemm_nt",))
             train_step(m, opt, batch)
@@ -422,7 +474,8 @@ def main():
                 c[0] += 1; c[1] += ms * 1e-3; c[2] += meta[1]; c[3] += meta[3]
         roof = None
         roof_reason = ("ranks share a device (gloo backend, fewer GPUs than ranks): HIP events around a launch also span the other "
-                       "process's time slices" if shared_device else "no gemm_nt launch was recorded")
+                       "process's time slices" if shared_device else "no gemm_nt launch was recorded" if a.full or a.breakdown else
+                       "not measured in a plain run (--full measures it)")
         if byvar:
             var, (nl, tsum, fsum, bsum) = max(byvar.items(), key=lambda kv: kv[1][1])
             assert tsum > 0 and fsum > 0, (var, nl, tsum, fsum)
@@ -508,7 +561,7 @@ def main():
             print("  gemm by shape (M, N, K, k, stride, mode; mode 2 = wgrad_tn): launches, ms, TFLOP/s", file=sys.stderr)
             for k, v in sorted(shapes.items(), key=lambda kv: -kv[1][1])[:60]:
                 print(f"    {str(k):44s} {v[0]:3d} {v[1]:8.3f} ms {v[2] / v[1] / 1e9:7.1f} TF", file=sys.stderr)
-        if world == 1 and not a.no_cpu_baseline and a.variant == "dvm":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.variant == "dvm":
             out["cpu_baseline"] = cpu_baseline(fl, a.classes, a.img, a.cpu_batch, max(1, a.cpu_steps))
             if a.cpu_b256 and a.cpu_batch != 256:
                 out["cpu_baseline_b256"] = cpu_baseline(fl, a.classes, a.img, 256, 1)

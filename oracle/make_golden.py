@@ -33,6 +33,7 @@ REF = os.environ.get("STIL_REFERENCE", "/root/reference")
 sys.path.insert(0, ROOT)
 sys.dont_write_bytecode = True
 
+from oracle import fixtures  # noqa: E402
 from oracle import stil_oracle as O  # noqa: E402
 
 
@@ -528,7 +529,7 @@ def main():
             fx["ssum_" + k] = np.float64(v.double().sum().item())
             fx["sabs_" + k] = np.float64(v.double().abs().sum().item())
         path = os.path.join(ROOT, "tests", "golden", name + ".npz")
-        np.savez_compressed(path, **fx)
+        fixtures.save(path, fx)
         n_none = sum(1 for g in ref_grads.values() if g is None)
         print(f"[{name}] oracle==reference OK  loss={float(ref_out['loss']):.6f}  mask1={int(o['mask1'].sum())}/{len(o['mask1'])} "
               f"case1={int(o['case1'].sum())} c2i={int(o['case2_i'].sum())} c2t={int(o['case2_t'].sum())} c3={int(o['case3'].sum())} "

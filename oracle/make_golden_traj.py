@@ -33,6 +33,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.dont_write_bytecode = True
 
+from oracle import fixtures  # noqa: E402
 from oracle import stil_oracle as O  # noqa: E402
 from oracle.make_golden import REF, SCALARS, craft_heads, install_stubs, randomize_state, ref_hparams  # noqa: E402
 
@@ -182,8 +183,8 @@ def main():
         out["o64_" + k] = np.array([r[k] for r in o64_steps], dtype=np.float64)          # the float64 oracle's value: a yardstick
         out["sens_" + k] = np.array([max(abs(pr[s_][k] - ora_steps[s_][k]) for pr, _ in pert_runs) for s_ in range(STEPS)], dtype=np.float64)
     path = os.path.join(ROOT, "tests", "golden", "traj_r18.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes; oracle==reference OK")
+    files = fixtures.save(path, out)
+    print("wrote", files, sum(os.path.getsize(f) for f in files), "bytes; oracle==reference OK")
 
 
 def sample(t):

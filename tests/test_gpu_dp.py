@@ -252,13 +252,13 @@ def test_bench_gpus_2_runs_two_ranks_end_to_end():
 
 
 def test_bench_line_single_gpu_carries_the_contract_fields():
-    """`python bench.py` as the driver calls it at N = 1 (tiny shapes here): ONE JSON line with the contract's keys, a `roofline`
+    """`python bench.py --full` at N = 1 (tiny shapes here): ONE JSON line with the contract's keys, a `roofline`
     object for the dominant gemm_nt instantiation measured with HIP events (structure and sanity ranges only: nothing that depends
     on how fast the box is) and a `cpu_baseline` object timed on the job's CPU share."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "STIL_DIST_BACKEND")}
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--img", "64", "--ncat", "3", "--ncon", "5", "--classes", "7",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "16", "--img", "64", "--ncat", "3", "--ncon", "5", "--classes", "7",
            "--cpu-steps", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     ctx = f"\nstdout: {r.stdout[-3000:]}\nstderr tail: {r.stderr[-3000:]}"
@@ -277,3 +277,32 @@ def test_bench_line_single_gpu_carries_the_contract_fields():
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "samples/s" and cb["value"] > 0 and 1 <= cb["cores"] <= (os.cpu_count() or 1), ctx
     assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] - 16 * 1e3) < 1e-2 * 16 * 1e3 and len(j["ms_per_step_by_rank"]) == 1, ctx
+
+
+def test_bench_plain_run_times_only_and_dumps_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) times the steps and prints the contract's line without the extra measurements
+    (`roofline` null with the reason, no `cpu_baseline`); `--dump-outputs DIR` writes what the last timed step computed as
+    float32 / float64 .npy files within 64 MB, the loss among them equal to the line's."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "STIL_DIST_BACKEND")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--img", "64", "--ncat", "3", "--ncon", "5",
+           "--classes", "7", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
+    ctx = f"\nstdout: {r.stdout[-3000:]}\nstderr tail: {r.stderr[-3000:]}"
+    assert r.returncode == 0, ctx
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, ctx
+    j = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, (k, ctx)
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and abs(j["value"] * j["ms_per_step"] - 16 * 1e3) < 1e-2 * 16 * 1e3, ctx
+    assert j["roofline"] is None and "--full" in j["roofline_reason"] and "cpu_baseline" not in j, ctx
+    files = sorted(p.name for p in out.iterdir())
+    assert {"loss.npy", "y_hat_m.npy", "flat_params.npy", "flat_grads.npy"} <= set(files), files
+    arrays = {f: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {f: a.dtype for f, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert abs(float(arrays["loss.npy"]) - j["loss"]) <= 1e-5 * (1 + abs(j["loss"])), (float(arrays["loss.npy"]), j["loss"])

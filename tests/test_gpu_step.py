@@ -162,6 +162,7 @@ def _check_flags(last, o, B_u):
 
 
 from oracle.make_golden import CASES, SCALARS, build_case, run_oracle64  # noqa: E402
+from oracle import fixtures  # noqa: E402
 from oracle import stil_oracle as O  # noqa: E402
 
 FWD_KEYS = ["y_hat_m", "y_hat_i", "y_hat_t", "x_si_enhance", "x_si", "x_ai", "x_st_enhance", "x_st", "x_at", "x_c", "feat_m", "feat_i",
@@ -173,7 +174,7 @@ FWD_KEYS = ["y_hat_m", "y_hat_i", "y_hat_t", "x_si_enhance", "x_si", "x_ai", "x_
 def test_training_step_matches_reference_golden(name):
     from stil_tta_amd.driver import train_step
     from stil_tta_amd.flat import StilAdam
-    fx = np.load(os.path.join(GOLD, name + ".npz"))
+    fx = fixtures.load(os.path.join(GOLD, name + ".npz"))
     hp, sd, batch, epoch, mask_random, mi_masks = build_case(name)
     m = _make_model(hp, sd)
     m.current_epoch = epoch
@@ -243,7 +244,7 @@ def test_training_step_with_split_k_matches_reference_golden(name):
     from stil_tta_amd import ops
     from stil_tta_amd.driver import train_step
     from stil_tta_amd.flat import StilAdam
-    fx = np.load(os.path.join(GOLD, name + ".npz"))
+    fx = fixtures.load(os.path.join(GOLD, name + ".npz"))
     outs = []
     default_split = ops._SPLITK
     try:
@@ -546,7 +547,7 @@ def test_configs1_full_size_backward_matches_oracle():
     from stil_tta_amd.driver import train_step
     from stil_tta_amd.flat import StilAdam
     hp, sd0, batch, mr, mm, o_fwd = _full_size_case("configs1_b256", CONFIGS1, 256, (31, 32, 33, 6))
-    fx = np.load(os.path.join(GOLD, "dvm_r50_b32_224.npz"))
+    fx = fixtures.load(os.path.join(GOLD, "dvm_r50_b32_224.npz"))
     m = _make_model(hp, {k: v.clone() for k, v in sd0.items()})
     m.current_epoch = 1
     with _trace_decisions() as trace:
@@ -670,7 +671,7 @@ def test_five_step_trajectory_matches_oracle():
     from stil_tta_amd.driver import train_step
     from stil_tta_amd.flat import StilAdam
     from oracle import make_golden_traj as T
-    fx = np.load(os.path.join(GOLD, "traj_r18.npz"))
+    fx = fixtures.load(os.path.join(GOLD, "traj_r18.npz"))
     hp, sd, batches, masks = T.build()
     assert int(fx["steps"]) == T.STEPS and int(fx["B"]) == T.B
     m = _make_model(hp, sd)

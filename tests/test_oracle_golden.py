@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import fixtures
 from oracle import stil_oracle as O
 from oracle.make_golden import CASES, SCALARS, TENSORS, build_case
 
@@ -22,7 +23,7 @@ def _close(a, b, tol):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_oracle_matches_reference_golden(name):
-    fx = np.load(os.path.join(GOLD, name + ".npz"))
+    fx = fixtures.load(os.path.join(GOLD, name + ".npz"))
     hp, sd, batch, epoch, mask_random, mi_masks = build_case(name)
     assert int(fx["meta_epoch"]) == epoch
     out = O.full_step(sd, {}, 1, batch, hp, epoch, mask_random, mi_masks)
@@ -53,7 +54,7 @@ def test_oracle_trajectory_matches_reference_golden():
     final state on the stored strided sample.  Oracle and reference share ATen's CPU kernels, so the bar is tight; the device
     test (tests/test_gpu_step.py) uses the float64 yardsticks stored beside the reference's values."""
     from oracle import make_golden_traj as T
-    fx = np.load(os.path.join(GOLD, "traj_r18.npz"))
+    fx = fixtures.load(os.path.join(GOLD, "traj_r18.npz"))
     hp, sd, batches, masks = T.build()
     steps, state = T.run_oracle(hp, sd, batches, masks)
     for s_ in range(T.STEPS):
