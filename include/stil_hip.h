@@ -393,6 +393,23 @@ int stil_aug_resize(const unsigned char* src_u8, const float* src_f32, const int
                     const float* jitter, const float* gmean, float* out, int B, int H, int W, int P, float scale,
                     void* stream);
 
+/* ---- device-resident step state (what a captured hipGraph must not bake in) -----------------------------------------------
+ * Positions and counts are int64 in DEVICE memory; the copy launch reads the old value, a second one-thread launch (stream order)
+ * advances it, so a replayed step writes the slot the eager step would.
+ * ring_enqueue: rows [n, D] into a ring of Q slots at *ptr.  layout 1: bank [D, Q] (slot = column, the Match queues), 0: bank
+ *   [Q, D] (slot = row, the distribution-alignment queues).  mode 0: truncated at the ring end, the first min(n, Q - p) rows
+ *   (_dequeue_and_enqueue of comatch_model.py:114-145, MMatch.py:102-117); 1: wrapped, row i -> (p + i) % Q (n <= Q).
+ *   advance != 0: then *ptr = (p + written) % Q and, when `count` is given, *count = min(*count + written, Q); advance == 0 only
+ *   reads *ptr (a second bank filled at the same position before the advancing call).
+ * queue_mean: out[k] = mean of queue[0:r, k] over r = min(*count, L) rows -- bit for bit stil_colsum(queue, r rows, scale 1 / r).
+ * rows_append: src [n, K] scores and target[n] appended at row *count of a [capacity, K] / [capacity] store; *count += n and
+ *   *overflow = 1 when the store is full (rows past the capacity are dropped). */
+int stil_ring_enqueue(float* bank, const float* rows, int n, int D, int Q, int layout, int mode, long long* ptr,
+                      long long* count, int advance, void* stream);
+int stil_queue_mean(const float* queue, int L, int K, const long long* count, float* out, void* stream);
+int stil_rows_append(const float* src, const long long* target, int n, int K, float* dst, long long* dst_target,
+                     int capacity, long long* count, int* overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

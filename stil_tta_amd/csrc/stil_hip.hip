@@ -10,7 +10,7 @@ void stil_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* stil_last_error(void) { return g_err; }
-extern "C" int stil_version(void) { return 104; }   // round 4: stil_gemm_nt gained bstats / scale_var / split_ws, stil_weight_layouts, stil_bn_train_bwd_tiles
+extern "C" int stil_version(void) { return 105; }   // 105: stil_ring_enqueue, stil_queue_mean, stil_rows_append (device-resident step state)
 // number of HIP devices visible (0 = none): lets the host fail loudly before any launch
 extern "C" int stil_device_count(void) {
   int n = 0;
@@ -26,3 +26,4 @@ extern "C" int stil_device_count(void) {
 #include "optim.hip"
 #include "augment.hip"
 #include "layout.hip"
+#include "state.hip"

@@ -192,6 +192,112 @@ def wants_graph(batch: int, img_size: int) -> bool:
     return batch * img_size * img_size <= 524288
 
 
+LAUNCHES = ("auto", "eager", "graph")
+
+
+def choose_launch(launch: str, batch: int, img_size: int, capturable: bool, world: int) -> str:
+    """"eager" or "graph" for a step of `batch` samples per GPU at `img_size` px.  auto: graph when the step is launch-bound
+    (wants_graph), the model can be captured (capture_key / capture_state) and there is one rank; eager otherwise.
+    "graph" with more than one rank raises: a captured step would bake in the data-parallel collectives, which are not captured."""
+    if launch not in LAUNCHES:
+        raise ValueError(f"launch must be one of {LAUNCHES}, got {launch!r}")
+    if launch == "eager":
+        return "eager"
+    if launch == "graph":
+        if world > 1:
+            raise ValueError(f"launch='graph' runs on one rank only (world size {world}): the data-parallel gradient exchange "
+                             "(RCCL collectives) is not captured into a hipGraph; use launch='eager' or 'auto'")
+        if not capturable:
+            raise ValueError("launch='graph': this model does not declare capture_key() / capture_state(); use launch='eager'")
+        return "graph"
+    return "graph" if world == 1 and capturable and wants_graph(batch, img_size) else "eager"
+
+
+def is_capturable(model) -> bool:
+    """Does the model declare what a capture bakes in (capture_key) and which device tensors a step changes (capture_state)?"""
+    return callable(getattr(model, "capture_key", None)) and callable(getattr(model, "capture_state", None))
+
+
+def batch_geometry(batch):
+    """(samples per GPU, image side) of a training batch: per top-level part ('l', 'u'), the leading dimension of its first
+    image tensor (4-D leaf); the image side is the largest last dimension of any image tensor.  Both layouts: STiL's
+    (views, tables, y, orig, identify) and the Match baselines' ((x, y, index), ((views...), y))."""
+    rows, side = 0, 0
+    for part in (batch.values() if isinstance(batch, dict) else [batch]):
+        leaves = [t for t in _leaves(part) if torch.is_tensor(t) and t.dim() == 4]
+        if leaves:
+            rows += int(leaves[0].shape[0])
+            side = max([side] + [int(t.shape[-1]) for t in leaves])
+    return rows, side
+
+
+def _leaves(obj):
+    if isinstance(obj, dict):
+        for v in obj.values():
+            yield from _leaves(v)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            yield from _leaves(v)
+    else:
+        yield obj
+
+
+def _tree_clone(obj, dev):
+    if torch.is_tensor(obj):
+        return obj.to(dev).clone()
+    if isinstance(obj, dict):
+        return {k: _tree_clone(v, dev) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_tree_clone(v, dev) for v in obj)
+    return obj
+
+
+def _tree_spec(obj):
+    """Structure, tensor shapes / dtypes and non-tensor values: two batches with the same spec fit the same static buffers."""
+    if torch.is_tensor(obj):
+        return ("T", tuple(obj.shape), obj.dtype)
+    if isinstance(obj, dict):
+        return ("D", tuple((k, _tree_spec(v)) for k, v in obj.items()))
+    if isinstance(obj, (list, tuple)):
+        return ("L", tuple(_tree_spec(v) for v in obj))
+    return ("V", obj)
+
+
+class EagerTrainStep:
+    """train_step behind the make_step interface: step(batch) -> loss."""
+    launch = "eager"
+
+    def __init__(self, model, optimizer):
+        self.model, self.optimizer = model, optimizer
+
+    def __call__(self, batch):
+        return train_step(self.model, self.optimizer, batch)
+
+
+def make_step(model, optimizer, example_batch, launch: str = "auto", warmup: int = 2):
+    """The training step for batches shaped like `example_batch`: step(batch) -> loss (detached; no host sync).
+    launch = "eager" (train_step), "graph" (GraphedTrainStep: the whole step captured into a hipGraph and replayed) or "auto"
+    (choose_launch: graph for launch-bound per-GPU steps of a capturable model on one rank).  The returned object's `launch`
+    attribute says which was chosen."""
+    rows, side = batch_geometry(example_batch)
+    kind = choose_launch(launch, rows, side, is_capturable(model), world_size())
+    if kind == "graph":
+        return GraphedTrainStep(model, optimizer, example_batch, warmup=warmup)
+    return EagerTrainStep(model, optimizer)
+
+
+_warmup_streams = {}
+
+
+def _warmup_stream(device):
+    """ONE warm-up stream per device for every capture: the deferred-reduction arena and the workspaces are kept per stream, so a
+    fresh stream per capture would leave one more arena behind at every re-capture."""
+    st = _warmup_streams.get(device)
+    if st is None:
+        st = _warmup_streams[device] = torch.cuda.Stream(device)
+    return st
+
+
 class GraphedTrainStep:
     """The whole optimisation step (zero_grad -> training_step -> backward -> all-reduce -> Adam) captured ONCE into a
     hipGraph and replayed: ~1500 kernel launches per step collapse into one graph launch, which is what matters when
@@ -201,56 +307,87 @@ class GraphedTrainStep:
     gradients beside the input-gradient chain: ops._SideStream forks and joins are captured as graph dependencies);
     the default captures every launch inline (faster for the small per-GPU batches graphs are for, ops._SideStream).
 
-    Static shapes only; the batch is copied into static device buffers before each replay.  Everything that varies per
-    step lives in device memory (mask-RNG step counter, Adam step counts); what is baked in at capture -- learning rate,
-    `current_epoch > start_epoch`, the set of parameters that receive gradients -- is watched, and a change triggers a
-    re-capture.  Not supported: `DA: True` (host read of the queue pointer, as in the reference).
-    """
+    Every tensor leaf of the batch is copied into static device buffers before each replay; a batch of another shape (the
+    ragged last batch of an epoch) runs eagerly instead -- everything a step changes lives in device memory (ring pointers,
+    queues, metric stores, mask-RNG step counter, Adam step counts), so eager and replayed steps mix freely.  What a capture
+    bakes in -- the learning rate, the model's capture_key() (loss terms chosen on the host from the epoch), the set of
+    parameters that receive gradients -- is watched, and a change triggers a re-capture, which releases the previous graph.
+    The warm-up steps before a capture are real steps: model.capture_state() is snapshotted before and restored after.
+    One rank only (choose_launch)."""
+    launch = "graph"
 
     def __init__(self, model, optimizer, example_batch, warmup: int = 2):
+        if world_size() > 1:
+            choose_launch("graph", 0, 0, True, world_size())   # raises: captured collectives are not supported
+        if not is_capturable(model):
+            choose_launch("graph", 0, 0, False, 1)
         self.model, self.optimizer = model, optimizer
         model.setup_device()
-        dev = model.prototypes.device
-        self.static = {k: ([v[0][0].to(dev).clone(), v[0][1].to(dev).clone()], [v[1][0].to(dev).clone(), v[1][1].to(dev).clone()],
-                           v[2].to(dev).clone(), v[3].to(dev).clone(), v[4].to(dev).clone()) for k, v in example_batch.items()}
+        dev = model.flat.params.device
+        self.static = _tree_clone(example_batch, dev)
+        self._spec = _tree_spec(self.static)
         self.warmup = warmup
         self.graph = None
+        self.loss = None
         self._key = None
+        self._logged, self._last = {}, {}
+        self.captures = 0      # how often the step was (re-)captured
+        self.eager_steps = 0   # batches of another shape, run eagerly
 
     def _signature(self):
         g = self.optimizer.param_groups[0]
-        return (float(g["lr"]), self.model.current_epoch > self.model.hp.start_epoch, self.model.flat._active_host)
+        return (float(g["lr"]), self.model.capture_key(), self.model.flat._active_host)
 
-    def _snapshot(self):
-        m, f = self.model, self.model.flat
-        tensors = [f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.ema, f.steps, m.prototypes_sum, m.prototypes_count_sum, m._rng_step]
-        tensors += list(f.s_counters) + list(f.t_counters)
-        return [(t, t.clone()) for t in tensors]
+    def _release(self):
+        """Drop the previous graph and every reference into its memory pool."""
+        m = self.model
+        for k, v in self._logged.items():
+            if m.logged.get(k) is v:
+                del m.logged[k]
+        if m.last is self._last:
+            m.last = {}
+        self.graph, self.loss, self._logged, self._last = None, None, {}, {}
 
     def _capture(self):
         from . import ops
-        snap = self._snapshot()  # warm-up steps are real optimisation steps: their effect is rolled back below
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        # gradient slab reductions are deferred to one multi-job launch per step (ops._DeferredReduce): in the warm-up too, which
-        # sizes the arena the capture then bakes in
-        with torch.cuda.stream(side), ops.deferring():  # eager warm-up on a side stream (allocator + lazy one-time setup), as PyTorch requires
-            for _ in range(self.warmup):
-                train_step(self.model, self.optimizer, self.static)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph), ops.deferring():  # records the step; nothing executes until replay()
-            self.loss = train_step(self.model, self.optimizer, self.static)
+        m = self.model
+        self._release()
+        snap = [(t, t.clone()) for t in m.capture_state()]  # warm-up steps are real optimisation steps: rolled back below
+        cur = torch.cuda.current_stream()
+        side = _warmup_stream(cur.device)
+        side.wait_stream(cur)
+        m._graph_step = True   # warm-up and capture run the step a replay runs (train metrics only into reserved stores)
+        try:
+            # gradient slab reductions are deferred to one multi-job launch per step (ops._DeferredReduce): in the warm-up too,
+            # which sizes the arena the capture then bakes in
+            with torch.cuda.stream(side), ops.deferring():  # eager warm-up on a side stream (allocator + lazy one-time setup)
+                for _ in range(self.warmup):
+                    train_step(m, self.optimizer, self.static)
+            cur.wait_stream(side)
+            torch.cuda.synchronize()
+            before = dict(m.logged)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph), ops.deferring():  # records the step; nothing executes until replay()
+                self.loss = train_step(m, self.optimizer, self.static)
+        finally:
+            m._graph_step = False
+        self._logged = {k: v for k, v in m.logged.items() if before.get(k) is not v}
+        self._last = m.last
         self._key = self._signature()
+        self.captures += 1
         for t, c in snap:
             t.copy_(c)
 
     def __call__(self, batch):
-        for k in ("l", "u"):
-            s, b = self.static[k], batch[k]
-            s[0][1].copy_(b[0][1], non_blocking=True); s[1][1].copy_(b[1][1], non_blocking=True); s[2].copy_(b[2], non_blocking=True)
+        if _tree_spec(batch) != self._spec:
+            self.eager_steps += 1
+            return train_step(self.model, self.optimizer, batch)
+        for s, b in zip(_leaves(self.static), _leaves(batch)):
+            if torch.is_tensor(s) and s is not b:
+                s.copy_(b, non_blocking=True)
         if self.graph is None or self._key != self._signature():
             self._capture()
         self.graph.replay()
+        self.model.logged.update(self._logged)
+        self.model.last = self._last
         return self.loss

@@ -25,7 +25,7 @@ from typing import Dict, Iterable, Iterator, Optional
 import torch
 import torch.distributed as dist
 
-from .driver import sync_buffers, train_step, world_size
+from .driver import make_step, sync_buffers, world_size
 
 
 # ------------------------------------------------------------------------------------------ host-side helpers
@@ -197,9 +197,13 @@ def validate(model, val_loader, limit_batches: Optional[int] = None) -> Dict[str
 def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable] = None, *, max_epochs: Optional[int] = None,
         eval_metric: str = "acc", logdir: Optional[str] = None, check_val_every_n_epoch: int = 1, val_check_interval: float = 1.0,
         sweep: bool = False, limit_train_batches: Optional[int] = None, limit_val_batches: Optional[int] = None,
-        resume_from: Optional[str] = None, verbose: bool = True, prefetch: bool = True) -> dict:
+        resume_from: Optional[str] = None, verbose: bool = True, prefetch: bool = True, launch: str = "eager") -> dict:
     """Trainer.fit(model, {'l','u'}, val_loader) of trainers/evaluate.py:178-179.  Returns the run summary
-    (best score / epoch, checkpoint path, last callback metrics, why it stopped)."""
+    (best score / epoch, checkpoint path, last callback metrics, why it stopped).
+    `launch` (driver.make_step): "eager" (default), "graph" (every step of the first batch's shapes replayed from a captured
+    hipGraph, one rank only; other shapes, e.g. a ragged last batch, run eagerly) or "auto" (driver.choose_launch).  A replayed
+    run computes what the eager run computes, bit for bit; its training AUROCs keep their scores in device stores reserved for
+    one epoch (steps per epoch x samples per step)."""
     model.setup_device()
     dev = model.prototypes.device
     conf = model.configure_optimizers()
@@ -220,6 +224,10 @@ def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable
     last_val: Dict[str, float] = {}
     lrs: Dict[int, float] = {}
     plateau = isinstance(sched, torch.optim.lr_scheduler.ReduceLROnPlateau)  # scheduler: linear (monitors the validation metric)
+    step = None
+    steps_per_epoch = max(len(v) for v in train_loaders.values())
+    if limit_train_batches is not None:
+        steps_per_epoch = min(steps_per_epoch, int(limit_train_batches))
     for epoch in range(start_epoch, max_epochs):
         model.train()
         model.current_epoch = epoch
@@ -231,7 +239,13 @@ def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable
         for i, batch in enumerate(stream):
             if limit_train_batches is not None and i >= limit_train_batches:
                 break
-            train_step(model, opt, _to_device(batch, dev))
+            batch = _to_device(batch, dev)
+            if step is None:
+                step = make_step(model, opt, batch, launch=launch)
+                if step.launch == "graph" and getattr(model.hp, "train_metrics", False):
+                    from .driver import batch_geometry
+                    model.reserve_train_metrics(max(1, steps_per_epoch) * batch_geometry(batch)[0])
+            step(batch)
             gstep += 1
         model.training_epoch_end()
         if sched is not None and not plateau:
@@ -253,7 +267,8 @@ def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable
     if world_size() > 1:
         dist.barrier()
     return dict(best_score=ckpt.best, best_epoch=ckpt.best_epoch, checkpoint=ckpt.path, epochs_run=epoch + 1 - start_epoch if max_epochs > start_epoch else 0,
-                global_step=gstep, stopped=stopped, callback_metrics=last_val, best_val_score=model.best_val_score, lr_by_epoch=lrs)
+                global_step=gstep, stopped=stopped, callback_metrics=last_val, best_val_score=model.best_val_score, lr_by_epoch=lrs,
+                launch=step.launch if step is not None else None)
 
 
 def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Optional[int] = None) -> Dict[str, float]:

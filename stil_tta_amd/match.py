@@ -159,7 +159,7 @@ class _MatchBase(STiLModel):
         return mask
 
     def _train_metrics(self, logits_x, y_l, logits_u, y_u):
-        if self.hp.train_metrics and not torch.cuda.is_current_stream_capturing():
+        if self._train_metrics_on():
             px, pu = self._metric_probs(logits_x), self._metric_probs(logits_u)
             self.acc_train(px, y_l); self.auc_train(px, y_l)
             self.acc_train_unlabelled(pu, y_u); self.auc_train_unlabelled(pu, y_u)
@@ -169,7 +169,7 @@ class _MatchBase(STiLModel):
 
     def training_epoch_end(self, _=None):
         """CoMatch.py:143-158 / SimMatch.py:124-139: epoch metrics."""
-        if self.hp.train_metrics and self.auc_train.preds:
+        if self.hp.train_metrics and self.auc_train.has_updates():
             for name, met in (("eval.train.acc", self.acc_train), ("eval.train.auc", self.auc_train),
                               ("eval.train_unlabelled.acc", self.acc_train_unlabelled), ("eval.train_unlabelled.auc", self.auc_train_unlabelled)):
                 self.log(name, met.compute(), on_epoch=True, on_step=False)
@@ -236,14 +236,15 @@ class CoMatchModel(nn.Module):
         self.register_buffer("queue_ptr_w", torch.zeros(1, dtype=torch.long))
         self.register_buffer("probs_xu", torch.zeros(K, Q))
         # distribution-alignment history: a Python list on the reference module (not in its state_dict either)
+        # ... here a ring on the device with its next slot and its fill count (so that a replayed step advances them too)
         self.register_buffer("_hist", torch.zeros(self.HIST, K), persistent=False)
-        self._hist_n = 0
-        self._hist_pos = 0
+        self.register_buffer("_hist_pos", torch.zeros(1, dtype=torch.long), persistent=False)
+        self.register_buffer("_hist_n", torch.zeros(1, dtype=torch.long), persistent=False)
 
     @property
     def hist_prob(self):
         """The reference's list view (oldest first)."""
-        n, pos = self._hist_n, self._hist_pos
+        n, pos = int(self._hist_n), int(self._hist_pos)
         order = [(pos - n + i) % self.HIST for i in range(n)]
         return [self._hist[i].clone() for i in order]
 
@@ -253,7 +254,8 @@ class CoMatchModel(nn.Module):
         self._hist.zero_()
         for i, r in enumerate(rows):
             self._hist[i].copy_(r)
-        self._hist_n, self._hist_pos = len(rows), len(rows) % self.HIST
+        self._hist_n.fill_(len(rows))
+        self._hist_pos.fill_(len(rows) % self.HIST)
 
 
 class CoMatch(_MatchBase):
@@ -264,23 +266,19 @@ class CoMatch(_MatchBase):
                                              eval_datatype="imaging_and_tabular"))
         self.model = CoMatchModel(hp, self.field_lengths)
         self.initialize_metrics(hp.num_classes, hp.num_classes)
-        self._ptr_s: Optional[int] = None  # host mirrors of the queue pointers (read once; the reference syncs every step)
-        self._ptr_w: Optional[int] = None
 
-    def load_state_dict(self, sd, strict=True):
-        self._ptr_s = self._ptr_w = None
-        return super().load_state_dict(sd, strict)
+    def capture_key(self):
+        """The host values a captured step bakes in: the contrastive weight min(epoch + 1, lam_c) and epoch > start_epoch
+        (loss terms, memory-smoothed pseudo-labels)."""
+        epoch = self.current_epoch
+        return (min(epoch + 1, self.hp.lam_c), epoch > self.hp.start_epoch, bool(self.training))
 
-    def _enqueue(self, queue, bank, ptr_buf, ptr, z, t):
-        """_dequeue_and_enqueue (comatch_model.py:114-145): truncated at the end of the ring."""
-        z, t = _gather_rows(z), _gather_rows(t)
+    def _enqueue(self, queue, bank, ptr_buf, z, t):
+        """_dequeue_and_enqueue (comatch_model.py:114-145): truncated at the end of the ring; the pointer stays on the device."""
+        z, t = _gather_rows(z).contiguous(), _gather_rows(t).contiguous()
         Q = queue.shape[1]
-        n = min(z.shape[0], Q - ptr)
-        queue[:, ptr:ptr + n] = z[:n].t()
-        bank[:, ptr:ptr + n] = t[:n].t()
-        ptr = (ptr + n) % Q
-        ptr_buf.fill_(ptr)
-        return ptr
+        lib().ring_enqueue(_p(queue), _p(z), z.shape[0], z.shape[1], Q, 1, 0, _p(ptr_buf), None, 0, _stream())
+        lib().ring_enqueue(_p(bank), _p(t), t.shape[0], t.shape[1], Q, 1, 0, _p(ptr_buf), None, 1, _stream())
 
     def training_step(self, batch, _=None):
         hp, M = self.hp, self.model
@@ -306,11 +304,10 @@ class CoMatch(_MatchBase):
             if _world() > 1:
                 dist.all_reduce(mean)
                 mean = mean / _world()
-            M._hist[M._hist_pos].copy_(mean)
-            M._hist_pos = (M._hist_pos + 1) % M.HIST
-            M._hist_n = min(M._hist_n + 1, M.HIST)
+            mean = mean.contiguous()
+            lib().ring_enqueue(_p(M._hist), _p(mean), 1, K, M.HIST, 0, 1, _p(M._hist_pos), _p(M._hist_n), 1, _stream())
             havg = torch.empty((K,), dtype=torch.float32, device=dev)
-            ops.colsum(M._hist, havg, M._hist_n, K, scale=1.0 / M._hist_n)
+            lib().queue_mean(_p(M._hist), M.HIST, K, _p(M._hist_n), _p(havg), _stream())   # mean of the filled rows
             probs_orig = torch.empty_like(probs0)
             lib().da_apply(_p(probs0), _p(havg), _p(probs_orig), btu, K, _stream())
             probs = probs_orig
@@ -326,11 +323,9 @@ class CoMatch(_MatchBase):
         S = ops.MatmulNTFn.apply(features_u_s0, keys, 1.0 / T)                                      # log(sim)
         loss_contrast = ops.ContrastGraphFn.apply(S, Q, float(hp.contrast_th))                      # CoMatch.py:104-117
         with torch.no_grad():
-            if self._ptr_s is None:
-                self._ptr_s, self._ptr_w = int(M.queue_ptr_s), int(M.queue_ptr_w)
-            self._ptr_s = self._enqueue(M.queue_s, M.probs_u, M.queue_ptr_s, self._ptr_s, features_u_s1, probs)
+            self._enqueue(M.queue_s, M.probs_u, M.queue_ptr_s, features_u_s1, probs)
             probs_xu = torch.cat([torch.nn.functional.one_hot(y_l, K).to(torch.float32), probs_orig], dim=0)
-            self._ptr_w = self._enqueue(M.queue_w, M.probs_xu, M.queue_ptr_w, self._ptr_w, feature_xu_w, probs_xu)
+            self._enqueue(M.queue_w, M.probs_xu, M.queue_ptr_w, feature_xu_w, probs_xu)
             mask = self._confidence(probs, hp.co_threshold)                                         # CoMatch.py:92-94
         loss_x = ops.CEHardFn.apply(outputs_x, y_l)
         loss_u = ops.CESoftFn.apply(outputs_u_s0, probs, mask)                                      # CoMatch.py:97-98

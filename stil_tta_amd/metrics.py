@@ -62,6 +62,12 @@ class Accuracy:
         if self.counts is not None:
             self.counts.zero_()
 
+    def state_tensors(self, device=None) -> List[torch.Tensor]:
+        """The device counters an update writes, created (zero) on `device` if no update has happened yet."""
+        if self.counts is None and device is not None:
+            self.counts = torch.zeros(2, dtype=torch.int64, device=device)
+        return [] if self.counts is None else [self.counts]
+
 
 class AUROC:
     """torchmetrics.AUROC(task='binary') / (task='multiclass', num_classes=K, average='macro'), exact mode."""
@@ -72,6 +78,32 @@ class AUROC:
         self.preds: List[torch.Tensor] = []
         self.target: List[torch.Tensor] = []
         self.per_class: Optional[torch.Tensor] = None
+        self.store = None   # reserve(): (scores [capacity, K], targets [capacity], int64 row count, int32 overflow flag) on the device
+
+    def reserve(self, capacity: int, device, K: Optional[int] = None) -> None:
+        """Preallocate room for `capacity` rows: updates then append on the device at a device-held row count
+        (stil_rows_append), which a captured hipGraph can replay; compute() raises if more rows arrived than fit.
+        Without a reservation the scores are kept in a Python list, as before."""
+        K = 1 if self.task == "binary" else int(self.num_classes if K is None else K)
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("AUROC.reserve: capacity must be positive")
+        if self.preds:
+            raise RuntimeError("AUROC.reserve: scores are already accumulated in the list; reset() first")
+        self.store = (torch.empty((capacity, K), dtype=torch.float32, device=device), torch.empty((capacity,), dtype=torch.int64, device=device),
+                      torch.zeros(1, dtype=torch.int64, device=device), torch.zeros(1, dtype=torch.int32, device=device))
+
+    @property
+    def reserved(self) -> bool:
+        return self.store is not None
+
+    def state_tensors(self) -> List[torch.Tensor]:
+        """The device tensors an update writes (a captured step's warm-up snapshot restores them)."""
+        return [] if self.store is None else list(self.store)
+
+    def has_updates(self) -> bool:
+        """Did anything arrive since the last reset()?  (Reads the device row count when reserved: one host sync.)"""
+        return bool(self.preds) or (self.store is not None and int(self.store[2].item()) > 0)
 
     def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
         p, y = _prep(preds, target)
@@ -81,13 +113,29 @@ class AUROC:
             raise RuntimeError(f"multiclass AUROC expects preds [N, {self.num_classes}], got {tuple(p.shape)}")
         if p.shape[0] != y.shape[0]:
             raise RuntimeError("AUROC: preds / target length mismatch")
+        if self.store is not None:
+            sc, st, cnt, ovf = self.store
+            if p.shape[1] != sc.shape[1]:
+                raise RuntimeError(f"AUROC: {p.shape[1]} score columns for a store reserved with {sc.shape[1]}")
+            if p.shape[0] > 0:
+                lib().rows_append(_p(p), _p(y), p.shape[0], p.shape[1], _p(sc), _p(st), sc.shape[0], _p(cnt), _p(ovf), _stream())
+            return
         self.preds.append(p)
         self.target.append(y)
 
     __call__ = update
 
+    def _local(self):
+        if self.store is None:
+            return torch.cat(self.preds), torch.cat(self.target)
+        sc, st, cnt, ovf = self.store
+        n, full = int(cnt.item()), int(ovf.item())
+        if full or n > sc.shape[0]:
+            raise RuntimeError(f"AUROC: {n} rows arrived for a reservation of {sc.shape[0]} (AUROC.reserve)")
+        return sc[:n], st[:n]
+
     def _gathered(self):
-        p, y = torch.cat(self.preds), torch.cat(self.target)
+        p, y = self._local()
         if not _dist_on():
             return p, y
         n = torch.tensor([p.shape[0]], dtype=torch.int64, device=p.device)
@@ -104,7 +152,7 @@ class AUROC:
         return (torch.cat([t[: int(s)] for t, s in zip(ps, sizes)]), torch.cat([t[: int(s)] for t, s in zip(ys, sizes)]))
 
     def compute(self) -> torch.Tensor:
-        if not self.preds:
+        if not self.has_updates():
             raise RuntimeError("AUROC.compute() before any update")
         p, y = self._gathered()
         N, K = p.shape
@@ -120,3 +168,6 @@ class AUROC:
 
     def reset(self) -> None:
         self.preds, self.target = [], []
+        if self.store is not None:
+            self.store[2].zero_()
+            self.store[3].zero_()

@@ -125,7 +125,6 @@ class MMatch(STiLModel):
         self.best_val_score = 0
         self.flat: Optional[FlatState] = None
         self.last: Dict[str, torch.Tensor] = {}
-        self._ptr: Optional[int] = None  # host mirror of embed_queue_ptr (read once; the reference syncs every step)
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -143,9 +142,9 @@ class MMatch(STiLModel):
         self.flat = FlatState(self.model, mirror, [], device)
         return self
 
-    def load_state_dict(self, sd, strict=True):
-        self._ptr = None
-        return super().load_state_dict(sd, strict)
+    def capture_key(self):
+        """The host values a captured step bakes in: the loss terms (epoch > start_epoch) and the memory smoothing (epoch > 0)."""
+        return (self.current_epoch > self.hp.start_epoch, self.current_epoch > 0, bool(self.training))
 
     def optimizer_groups(self):
         return [self.model]   # Adam([{'params': self.model.parameters()}]) -- MMatch.py:385-387
@@ -190,14 +189,12 @@ class MMatch(STiLModel):
             loss = loss + hp.mmatch_lambda * (loss_i_u + loss_t_u)
 
         with torch.no_grad():
-            if hp.train_metrics and not torch.cuda.is_current_stream_capturing():
+            if self._train_metrics_on():
                 prob_m = self._metric_probs(y_m)
                 y_u_dev = y_u.to(dev)
                 self.acc_train(prob_m[:B_l], y_l); self.auc_train(prob_m[:B_l], y_l)
                 self.acc_train_unlabelled(prob_m[B_l:], y_u_dev); self.auc_train_unlabelled(prob_m[B_l:], y_u_dev)
             # _dequeue_and_enqueue (MMatch.py:102-117): every sample of the batch, truncated at the end of the ring
-            if self._ptr is None:
-                self._ptr = int(self.embed_queue_ptr)
             z = feat_m
             t = torch.cat((torch.nn.functional.one_hot(y_l, K).to(torch.float32), pseudo), dim=0)   # pseudo_label_all (MMatch.py:243)
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:       # concat_all_gather (MMatch.py:104-106)
@@ -206,11 +203,10 @@ class MMatch(STiLModel):
                 dist.all_gather(zs, z.contiguous())
                 dist.all_gather(ts, t.contiguous())
                 z, t = torch.cat(zs), torch.cat(ts)
-            n = min(z.shape[0], BANK - self._ptr)
-            self.embed_queue[:, self._ptr:self._ptr + n] = z[:n].t()
-            self.probs_queue[:, self._ptr:self._ptr + n] = t[:n].t()
-            self._ptr = (self._ptr + n) % BANK
-            self.embed_queue_ptr.fill_(self._ptr)
+            # the pointer stays on the device: both banks at embed_queue_ptr, then the pointer moves (stil_ring_enqueue, truncating)
+            z, t = z.contiguous(), t.contiguous()
+            lib().ring_enqueue(_p(self.embed_queue), _p(z), z.shape[0], z.shape[1], BANK, 1, 0, _p(self.embed_queue_ptr), None, 0, _stream())
+            lib().ring_enqueue(_p(self.probs_queue), _p(t), t.shape[0], t.shape[1], BANK, 1, 0, _p(self.embed_queue_ptr), None, 1, _stream())
 
         bs = B_l + B_u
         for name, v in (("CEloss", loss_ce), ("CEloss_unlabelled_i", loss_i_u), ("CEloss_unlabelled_t", loss_t_u), ("loss", loss)):
@@ -221,7 +217,7 @@ class MMatch(STiLModel):
 
     def training_epoch_end(self, _=None):
         """MMatch.py:265-276: epoch metrics only (no prototypes to commit)."""
-        if self.hp.train_metrics and self.auc_train.preds:  # something was accumulated this epoch
+        if self.hp.train_metrics and self.auc_train.has_updates():  # something was accumulated this epoch
             for name, met in (("eval.train.acc", self.acc_train), ("eval.train.auc", self.auc_train),
                               ("eval.train_unlabelled.acc", self.acc_train_unlabelled), ("eval.train_unlabelled.auc", self.auc_train_unlabelled)):
                 self.log(name, met.compute(), on_epoch=True, on_step=False)
@@ -385,7 +381,7 @@ class CoTraining(STiLModel):
         if self.current_epoch > hp.start_epoch:
             loss = loss + hp.rate_uce * (loss_i_u + loss_t_u)
         with torch.no_grad():
-            if hp.train_metrics and not torch.cuda.is_current_stream_capturing():
+            if self._train_metrics_on():
                 prob_m = self._metric_probs(y_m)
                 y_u_dev = y_u.to(dev)
                 self.acc_train(prob_m[:B_l], y_l); self.auc_train(prob_m[:B_l], y_l)

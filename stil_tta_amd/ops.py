@@ -320,19 +320,21 @@ class _DeferredReduce:
 
     def add(self, device, P: int, dst: torch.Tensor, splits, N, K, Cin, taps, Kdst, accumulate, scale):
         d = self._state(device)
-        if dst.data_ptr() in d["dsts"]:            # two contributions to one slot: in order
-            self._flush_one(d)
+        if dst.data_ptr() in d["dsts"]:            # two contributions to one slot: in order.  The arena offset is NOT rewound: this
+            self._flush_one(d, reset_off=False)    # job's partials (allocated before the flush) are still pending above it
         d["dsts"].add(dst.data_ptr())
         d["jobs"].append(self._JOB.pack(P, dst.data_ptr(), splits, N, K, Cin, taps, Kdst, accumulate, float(scale)))
 
-    def _flush_one(self, d):
+    def _flush_one(self, d, reset_off=True):
         if d["jobs"]:
             L = lib()
             assert L.reduce_job_bytes() == self._JOB.size, "StilReduceJob layout changed"
             blob = b"".join(d["jobs"])
             with torch.cuda.stream(d["stream"]):
                 L.reduce_jobs(blob, len(d["jobs"]), d["stream"].cuda_stream)
-        d["jobs"], d["dsts"], d["off"] = [], set(), 0
+        d["jobs"], d["dsts"] = [], set()
+        if reset_off:
+            d["off"] = 0
 
     def flush(self):
         for d in self.st.values():

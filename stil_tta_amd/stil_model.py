@@ -273,6 +273,49 @@ class STiLModel(_Base):
         """What decides which parameters receive gradients in backward (comm.GradExchange learns one plan per value)."""
         return (self.current_epoch > self.hp.start_epoch, bool(self.training))
 
+    # ------------------------------------------------------------------ captured steps (driver.GraphedTrainStep)
+    def capture_key(self):
+        """The host values a captured step bakes in (which loss terms run): a change re-captures the step."""
+        return (self.current_epoch > self.hp.start_epoch, bool(self.training))
+
+    def _train_metric_objs(self):
+        return [self.acc_train, self.auc_train, self.acc_train_unlabelled, self.auc_train_unlabelled]
+
+    def reserve_train_metrics(self, capacity: int):
+        """Device-held stores for `capacity` rows of each training AUROC: a captured step then updates the train metrics too."""
+        self.setup_device()
+        for met in self._train_metric_objs():
+            if isinstance(met, AUROC):
+                met.reserve(capacity, self.flat.params.device, self.hp.num_classes)
+
+    def _train_metrics_on(self) -> bool:
+        """Update the train metrics in this step?  Eagerly whenever hp.train_metrics; in a captured step (and its warm-up) only
+        when every training AUROC has a reservation (a Python list cannot be appended to by a replay)."""
+        if not self.hp.train_metrics:
+            return False
+        if not (getattr(self, "_graph_step", False) or torch.cuda.is_current_stream_capturing()):
+            return True
+        return all(m.reserved for m in self._train_metric_objs() if isinstance(m, AUROC))
+
+    def capture_state(self):
+        """Every device tensor a training step changes: the flat parameter / gradient / Adam / EMA slabs and step counts, all
+        module buffers (BN statistics, prototypes, queues, ring pointers, ...), the mask-RNG step counter and the train metrics'
+        stores.  driver.GraphedTrainStep snapshots them before a capture's warm-up steps and restores them after."""
+        self.setup_device()
+        f = self.flat
+        out = [f.params, f._grads, f.exp_avg, f.exp_avg_sq, f.ema, f.steps] + list(self.buffers()) + list(f.s_counters) + list(f.t_counters)
+        if getattr(self, "_rng_step", None) is not None:
+            out.append(self._rng_step)
+        if self.hp.train_metrics and all(m.reserved for m in self._train_metric_objs() if isinstance(m, AUROC)):
+            for met in self._train_metric_objs():
+                out += met.state_tensors(f.params.device) if isinstance(met, Accuracy) else met.state_tensors()
+        seen, uniq = set(), []
+        for t in out:
+            if id(t) not in seen:
+                seen.add(id(t))
+                uniq.append(t)
+        return uniq
+
     def project_3features(self, feat_m=None, feat_i=None, feat_t=None):  # STiLModel.py:182-192
         fm = ops.l2norm(self.projector_multimodal.run(feat_m)) if feat_m is not None else None
         fi = ops.l2norm(self.projector_imaging.run(feat_i)) if feat_i is not None else None
@@ -293,9 +336,9 @@ class STiLModel(_Base):
         if dist.is_available() and dist.is_initialized():
             dist.all_reduce(mean)
             mean = mean / dist.get_world_size()
-        ptr = int(self.DA_ptr)  # one host sync per step, as in the reference (STiLModel.py:175); DA is off by default
-        self.DA_queue[ptr].copy_(mean)
-        self.DA_ptr.fill_((ptr + 1) % self.DA_len)
+        # DA_queue[DA_ptr] = mean; DA_ptr = (DA_ptr + 1) % DA_len -- the pointer stays on the device (the reference reads it on
+        # the host, STiLModel.py:175), so a replayed step writes the next row too
+        lib().ring_enqueue(_p(self.DA_queue), _p(mean.contiguous()), 1, K, self.DA_len, 0, 1, _p(self.DA_ptr), None, 1, _stream())
         qmean = torch.empty((K,), dtype=torch.float32, device=dev)
         ops.colsum(self.DA_queue, qmean, self.DA_len, K, scale=1.0 / self.DA_len)
         out = torch.empty_like(probs)
@@ -462,7 +505,7 @@ class STiLModel(_Base):
                 dist.all_reduce(cs, op=dist.ReduceOp.SUM)  # ONE fused [K, Dp+1] collective instead of the reference's two
             lib().proto_add(_p(cs), _p(self.prototypes_sum), _p(self.prototypes_count_sum), K, hp.projection_dim, _stream())
 
-            if hp.train_metrics and not torch.cuda.is_current_stream_capturing():  # STiLModel.py:242, 359-362
+            if self._train_metrics_on():  # STiLModel.py:242, 359-362
                 prob_m = self._metric_probs(y_m)
                 y_u_dev = y_u.to(dev)
                 self.acc_train(prob_m[:B_l], y_l)
@@ -494,7 +537,7 @@ class STiLModel(_Base):
     def training_epoch_end(self, _=None):
         """STiLModel.py:389-421: prototypes <- sum / count (every class needs a confident sample), zero accumulators."""
         K, Dp = self.hp.num_classes, self.hp.projection_dim
-        if self.hp.train_metrics and self.auc_train.preds:  # something was accumulated this epoch  # STiLModel.py:393-405
+        if self.hp.train_metrics and self.auc_train.has_updates():  # something was accumulated this epoch  # STiLModel.py:393-405
             vals = {}
             for name, met in (("eval.train.acc", self.acc_train), ("eval.train.auc", self.auc_train),
                               ("eval.train_unlabelled.acc", self.acc_train_unlabelled), ("eval.train_unlabelled.auc", self.auc_train_unlabelled)):
