@@ -393,6 +393,38 @@ int stil_aug_resize(const unsigned char* src_u8, const float* src_f32, const int
                     const float* jitter, const float* gmean, float* out, int B, int H, int W, int P, float scale,
                     void* stream);
 
+/* ---- albumentations branch of the input pipeline (augmentation_speedup: True, utils/utils.py:46-256) -------------------
+ * albumentations 1.3.1 / OpenCV 4.x on HWC images with 3 channels: uint8 (DVM .npy) or float32 in [0,1] (cardiac .npy),
+ * exactly one of the *_u8 / *_f32 pointers non-null, destinations of the source type.  Draws are arguments; a sample whose
+ * op is off is copied bit for bit.  Pixel definitions: tests/alb_restate.py.
+ * stil_alb_color: A.ColorJitter (brightness, contrast, saturation, hue in the per-image order order[b] of 0..3,
+ *   factors[b] = (b, c, s, h) in double, applied where cj_on[b]) then A.ToGray (gray_on[b]) on whole images, in place or
+ *   src -> dst (utils/utils.py:52-53,146-147,224-225; ContrastiveImagingAndTabularDataset.py:184-196).  Two launches: the
+ *   grey sum the contrast op takes the mean of (per-workgroup partials in gpart [B, 64] doubles, integer for uint8), then the
+ *   chain.  wg_per_image: workgroups per image in [1, 64], 0 = chosen from B. */
+int stil_alb_color(const unsigned char* src_u8, const float* src_f32, unsigned char* dst_u8, float* dst_f32, int B, int H, int W,
+                   const int* order, const double* factors, const unsigned char* cj_on, const unsigned char* gray_on,
+                   double* gpart, int wg_per_image, void* stream);
+/* stil_alb_blur: A.GaussianBlur = cv2.GaussianBlur(img, (ksize, ksize), sigma[b]) (utils/utils.py:54,148,227,245): weights
+ *   exp(-x^2 / (2 sigma^2)) normalised in double, reflect-101 borders, one rounding for uint8; sigma[b] <= 0 copies.
+ *   ksize odd in [1, 31]; not in place. */
+int stil_alb_blur(const unsigned char* src_u8, const float* src_f32, unsigned char* dst_u8, float* dst_f32, int B, int H, int W,
+                  const double* sigma, int ksize, void* stream);
+/* stil_alb_resize: A.RandomResizedCrop / A.Resize + A.HorizontalFlip (utils/utils.py:55-56,190-191,222-223): crop
+ *   box[b] = (top, left, h, w), cv2 INTER_LINEAR to P x P, mirrored where flip[b] (may be null).  Output either dst (P x P HWC
+ *   of the source type) or out_chw, the final float [B,3,P,P] (convert_to_ts: float32(v / 255.0); convert_to_ts_01: a copy). */
+int stil_alb_resize(const unsigned char* src_u8, const float* src_f32, unsigned char* dst_u8, float* dst_f32, float* out_chw, int B,
+                    int H, int W, const int* box, const unsigned char* flip, int P, void* stream);
+/* stil_alb_rotate: A.Rotate(limit) = cv2.warpAffine(getRotationMatrix2D((W/2-0.5, H/2-0.5), angle, 1)) (utils/utils.py:82,
+ *   97,112,170): minv[b] = the inverted 2x3 map (stil_tta_amd.augment.alb_rotation_matrix), source position quantised to
+ *   1/32 pixel, bilinear, reflect-101, same size; on[b] == 0 copies; flip_first[b] (may be null): the A.HorizontalFlip
+ *   that precedes the rotation.  Not in place. */
+int stil_alb_rotate(const unsigned char* src_u8, const float* src_f32, unsigned char* dst_u8, float* dst_f32, int B, int H, int W,
+                    const double* minv, const unsigned char* on, const unsigned char* flip_first, void* stream);
+/* stil_alb_to_tensor: convert_to_ts / convert_to_ts_01 (utils/utils.py:33-42): HWC -> float CHW [B,3,H,W], uint8 as
+ *   float32(v / 255.0).  Only where the blur is the last stage (utils/utils.py:227-228,245-246); stil_alb_resize fuses it. */
+int stil_alb_to_tensor(const unsigned char* src_u8, const float* src_f32, float* out, int B, int H, int W, void* stream);
+
 /* ---- device-resident step state (what a captured hipGraph must not bake in) -----------------------------------------------
  * Positions and counts are int64 in DEVICE memory; the copy launch reads the old value, a second one-thread launch (stream order)
  * advances it, so a replayed step writes the slot the eager step would.

@@ -10,7 +10,7 @@ void stil_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* stil_last_error(void) { return g_err; }
-extern "C" int stil_version(void) { return 105; }   // 105: stil_ring_enqueue, stil_queue_mean, stil_rows_append (device-resident step state)
+extern "C" int stil_version(void) { return 106; }   // 106: stil_alb_* (albumentations branch of the input pipeline)
 // number of HIP devices visible (0 = none): lets the host fail loudly before any launch
 extern "C" int stil_device_count(void) {
   int n = 0;
@@ -25,5 +25,6 @@ extern "C" int stil_device_count(void) {
 #include "saint.hip"
 #include "optim.hip"
 #include "augment.hip"
+#include "augment_alb.hip"
 #include "layout.hip"
 #include "state.hip"
