@@ -296,6 +296,8 @@ int stil_proto_accum(const float* feat_e, const int* hard, const unsigned char* 
                      int B, int B_l, int K, int Dp, float repeat_ratio, void* stream);
 int stil_proto_add(const float* class_sum_cnt, float* prototypes_sum, float* prototypes_count_sum, int K,
                    int Dp, void* stream);
+/* epoch end: prototypes[k] = prototypes_sum[k] / prototypes_count_sum[k] for classes with count >= 1; a class with count < 1 keeps
+ * its prototype and adds one to *bad_count_dev (zeroed by the caller).  The accumulators are read only: the caller clears them. */
 int stil_proto_commit(float* prototypes, float* prototypes_sum, float* prototypes_count_sum,
                       int* bad_count_dev, int K, int Dp, void* stream);
 
@@ -343,7 +345,8 @@ int stil_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 
 /* ---- evaluation metrics (torchmetrics==0.11.0 as used by STiLModel.py:122-145, 360-363, 458-463, 529-545) ----
  * hits_total: device int64[2] = {hits, samples}, accumulated (integer atomics: order-independent).
- * metric_topk: target class within the k best scores of its row (k = 1: argmax's first-maximum rule).
+ * metric_topk: target class within the k best scores of its row (k = 1: argmax's first-maximum rule); k > K is accepted and
+ *        counts what k = K counts (every row whose target is a valid class).
  * metric_binary: (prob > threshold) == (target == 1).
  * auroc: exact area under the ROC curve (thresholds=None); K == 1: binary on scores[:,0] with positives target == 1;
  *        K > 1: one-vs-rest per class and their unweighted mean (macro; a class without positives or negatives

@@ -382,7 +382,8 @@ __global__ void proto_add_kernel(const float* __restrict__ cs, float* __restrict
   int k = i / (Dp + 1), c = i - k * (Dp + 1);
   if (c < Dp) psum[(long)k * Dp + c] += cs[i]; else pcnt[k] += cs[i];
 }
-// epoch end: prototypes = sum / count ; zero accumulators ; flag[0] = #classes with count < 1
+// epoch end: prototypes = sum / count where count >= 1; a class with count < 1 keeps its prototype and adds one to bad[0] (caller-zeroed).
+// The accumulators are only read: the caller zeroes them afterwards (STiLModel.training_epoch_end).
 __global__ void proto_commit_kernel(float* __restrict__ protos, float* __restrict__ psum, float* __restrict__ pcnt,
                                     int* __restrict__ bad, int K, int Dp) {
   int k = blockIdx.x;

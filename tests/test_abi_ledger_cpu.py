@@ -1,0 +1,191 @@
+"""Ledger of the C ABI: every `stil_*` entry point of include/stil_hip.h names the test function(s) that check it directly
+("file::function"), or carries a short reason why it has none.  A new entry point without an entry fails here; so does an
+entry whose test was renamed away.  DESIGN.md section 2 prints this table (python tests/test_abi_ledger_cpu.py)."""
+import ast
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+TESTS = os.path.dirname(os.path.abspath(__file__))
+
+MAX_REASONS = 12
+
+EP = "test_gpu_entry_points.py"
+OPS = "test_gpu_ops.py"
+CPU = "test_product_cpu.py"
+_DEFER = f"{OPS}::test_deferred_gradient_reductions_equal_the_immediate_ones_bit_for_bit"
+_BN_STATS = f"{OPS}::test_bn_statistics_two_pass_and_tile_paths_agree_with_float64"
+_BN_BWD = f"{OPS}::test_gemm_epilogue_batchnorm_backward_sums"
+_PLAN = f"{OPS}::test_weight_layout_plan_equals_the_per_call_layouts_bit_for_bit"
+_POLICY = f"{CPU}::test_small_batch_policies_host_side"
+_INFO = f"{EP}::test_size_queries_and_library_info"
+_AUG = "test_gpu_augment.py"
+_ALB = "test_gpu_augment_alb.py"
+_MATCH = "test_gpu_match.py"
+_MET = "test_gpu_metrics.py"
+
+# name -> list of "file::function" (checked directly there) | str (the reason it has no test of its own)
+LEDGER = {
+    "stil_last_error": [_INFO],
+    "stil_version": [_INFO, f"{CPU}::test_library_exports_every_declared_symbol"],
+    "stil_device_count": [_INFO],
+    "stil_gemm_nt": [f"{OPS}::test_gemm_nt_plain", f"{OPS}::test_conv_fwd_dgrad_wgrad", f"{OPS}::test_gemm_nt_wide_epilogue_is_the_scalar_one_bit_for_bit"],
+    "stil_gemm_nt_split_workspace_bytes": [f"{OPS}::test_gemm_split_k_is_the_unsplit_product_and_deterministic"],
+    "stil_gemm_nt_force_splits": [_POLICY],
+    "stil_gemm_nt_bstats_ok": "eligibility predicate of the bstats epilogue (no arithmetic); the launches it admits are compared in "
+                              "test_gemm_epilogue_batchnorm_backward_sums",
+    "stil_gemm_nt_tile_rows": [_BN_STATS, f"{CPU}::test_gemm_tune_policy_and_precision_flag_arithmetic"],
+    "stil_gemm_nt_variant": [f"{CPU}::test_c_abi_rejects_bad_arguments_without_a_gpu", f"{CPU}::test_gemm_tune_policy_and_precision_flag_arithmetic"],
+    "stil_gemm_nt_config": "reports which instantiation a launch takes (bench bookkeeping and profile labels, no arithmetic); read on every "
+                           "ops.gemm_nt call of the GEMM tests",
+    "stil_wgrad_workspace_bytes": [_INFO],
+    "stil_wgrad_tn": [f"{OPS}::test_conv_fwd_dgrad_wgrad", _DEFER],
+    "stil_reduce_job_bytes": [_POLICY],
+    "stil_wgrad_splits": [_POLICY, _INFO],
+    "stil_wgrad_force_splits": [_POLICY],
+    "stil_wgrad_tn_partial": [_DEFER],
+    "stil_colsum_chunks": [_INFO, _POLICY],
+    "stil_colsum_partial": [_DEFER],
+    "stil_reduce_jobs": [_DEFER, "test_gpu_graph_step.py::test_deferred_reduce_duplicate_slot_at_low_offset"],
+    "stil_colsum_workspace_bytes": [_INFO],
+    "stil_colsum": [f"{EP}::test_colsum", f"{EP}::test_queue_mean_is_colsum_bit_for_bit_and_the_float64_mean"],
+    "stil_conv_weight_layout": [f"{OPS}::test_conv_fwd_dgrad_wgrad", _PLAN],
+    "stil_conv_weight_layout_phase": [f"{OPS}::test_strided_dgrad_phase_decomposition", _PLAN],
+    "stil_weight_layouts": [_PLAN],
+    "stil_weight_layout_job_bytes": [_PLAN],
+    "stil_weight_layout_job_blocks": [_PLAN],
+    "stil_im2col_nchw": [f"{OPS}::test_stem_and_maxpool"],
+    "stil_transpose": [_PLAN],
+    "stil_bn_workspace_bytes": [_BN_STATS],
+    "stil_bn_train_fwd": [_BN_STATS, f"{OPS}::test_conv_bn_act_train_and_eval"],
+    "stil_bn_train_fwd_tiles": [_BN_STATS, f"{OPS}::test_deferred_batchnorm_is_the_materialised_path_bit_for_bit"],
+    "stil_bn_tiles_workspace_bytes": [_BN_STATS],
+    "stil_bn_eval_affine": [f"{EP}::test_bn_eval_affine"],
+    "stil_bn_train_bwd": [_BN_BWD, f"{OPS}::test_conv_bn_act_train_and_eval"],
+    "stil_bn_bwd_tiles_workspace_bytes": [_BN_BWD],
+    "stil_bn_train_bwd_tiles": [_BN_BWD],
+    "stil_maxpool3x3s2_fwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu"],
+    "stil_maxpool3x3s2_bwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu"],
+    "stil_layernorm_fwd": [f"{OPS}::test_layernorm"],
+    "stil_layernorm_bwd_workspace_bytes": "size of the per-block partials of stil_layernorm_bwd, whose block count is internal; a short workspace is "
+                                          "rejected inside test_layernorm",
+    "stil_layernorm_bwd": [f"{OPS}::test_layernorm"],
+    "stil_attention_fwd": [f"{OPS}::test_attention"],
+    "stil_attention_bwd": [f"{OPS}::test_attention"],
+    "stil_act_bwd": [f"{EP}::test_act_bwd"],
+    "stil_drop_add": [f"{EP}::test_drop_add_both_paths_all_operand_combinations", f"{EP}::test_drop_add_vector_and_scalar_paths_agree_bit_for_bit",
+                      f"{EP}::test_drop_add_backward"],
+    "stil_axpby": [f"{EP}::test_axpby_and_scale_dev"],
+    "stil_rng_mask": [f"{OPS}::test_rng_mask_rate_and_determinism"],
+    "stil_counter_inc": [f"{OPS}::test_rng_mask_rate_and_determinism"],
+    "stil_tab_embed_fwd": [f"{OPS}::test_tab_embed"],
+    "stil_tab_embed_bwd_workspace_bytes": [_INFO],
+    "stil_tab_embed_bwd": [f"{OPS}::test_tab_embed"],
+    "stil_tokmean_fwd": [f"{EP}::test_tokmean"],
+    "stil_tokmean_bwd": [f"{EP}::test_tokmean"],
+    "stil_saint_embed_fwd": [f"{OPS}::test_saint_pieces"],
+    "stil_saint_embed_bwd": [f"{OPS}::test_saint_pieces"],
+    "stil_colmlp_fwd": [f"{OPS}::test_saint_pieces"],
+    "stil_colmlp_bwd": [f"{OPS}::test_saint_pieces"],
+    "stil_geglu_fwd": [f"{EP}::test_geglu"],
+    "stil_geglu_bwd": [f"{EP}::test_geglu"],
+    "stil_row_softmax_fwd": [f"{EP}::test_row_softmax"],
+    "stil_row_softmax_bwd": [f"{EP}::test_row_softmax"],
+    "stil_ce_hard": [f"{EP}::test_ce_hard", f"{OPS}::test_small_losses"],
+    "stil_ce_soft": [f"{EP}::test_ce_soft", f"{OPS}::test_small_losses"],
+    "stil_reduce_sum": [f"{EP}::test_reduce_sum"],
+    "stil_scale_dev": [f"{EP}::test_axpby_and_scale_dev"],
+    "stil_l2norm_fwd": [f"{EP}::test_l2norm"],
+    "stil_l2norm_bwd": [f"{EP}::test_l2norm"],
+    "stil_clip_fwd": [f"{OPS}::test_clip_and_club"],
+    "stil_clip_bwd": [f"{OPS}::test_clip_and_club"],
+    "stil_club_fwd": [f"{OPS}::test_clip_and_club"],
+    "stil_club_bwd": [f"{OPS}::test_clip_and_club"],
+    "stil_cgpl_pgls": [f"{OPS}::test_cgpl_pgls_and_prototypes", f"{OPS}::test_cgpl_top1_is_argmax_of_softmax_with_first_index_ties"],
+    "stil_da_apply": [f"{EP}::test_da_apply"],
+    "stil_proto_loss": [f"{EP}::test_proto_loss", f"{EP}::test_proto_loss_at_its_lds_bound"],
+    "stil_proto_accum": [f"{OPS}::test_cgpl_pgls_and_prototypes"],
+    "stil_proto_add": [f"{EP}::test_proto_add_and_commit"],
+    "stil_proto_commit": [f"{EP}::test_proto_add_and_commit"],
+    "stil_contrast_graph": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch"],
+    "stil_simmatch_unfold": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch"],
+    "stil_freematch_update": [f"{_MATCH}::test_freematch_kernels_against_torch"],
+    "stil_freematch_entropy": [f"{_MATCH}::test_freematch_kernels_against_torch"],
+    "stil_flag_ratios": [f"{EP}::test_flag_ratios"],
+    "stil_onehot_argmax": [f"{OPS}::test_onehot_argmax_first_maximum_and_threshold"],
+    "stil_ema_update": [f"{OPS}::test_ema_and_adam_slabs"],
+    "stil_ema_int_trunc": [f"{EP}::test_ema_int_trunc"],
+    "stil_adam_step": [f"{OPS}::test_ema_and_adam_slabs"],
+    "stil_metric_topk": [f"{EP}::test_metric_topk_on_a_column_slice_and_k_edges", f"{_MET}::test_topk_accuracy_counts"],
+    "stil_metric_binary": [f"{EP}::test_metric_binary_at_the_threshold", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
+    "stil_auroc_workspace_bytes": [f"{EP}::test_auroc_single_row_and_all_scores_equal"],
+    "stil_auroc": [f"{EP}::test_auroc_single_row_and_all_scores_equal", f"{_MET}::test_multiclass_auroc", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
+    "stil_tab_corrupt": [f"{_AUG}::test_tab_corrupt_matches_reference_golden_bit_for_bit"],
+    "stil_tab_corrupt_draw": [f"{EP}::test_tab_corrupt_draw", f"{EP}::test_tab_corrupt_draw_rejects_more_than_8192_columns",
+                              f"{_AUG}::test_tab_corrupt_device_draws_are_valid_and_uniform"],
+    "stil_aug_gray_mean": [f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas"],
+    "stil_aug_blur": [f"{_AUG}::test_gaussian_blur_matches_torchvision_formula"],
+    "stil_aug_rotate": [f"{_AUG}::test_rotate_matches_bilinear_reflect101_restatement"],
+    "stil_aug_hue": [f"{_AUG}::test_hue_matches_torchvision_float_formulas"],
+    "stil_aug_resize": [f"{_AUG}::test_resize_crop_flip_matches_interpolate", f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas"],
+    "stil_alb_color": [f"{_ALB}::test_color_u8_brightness_contrast_all_orders_bit_exact", f"{_ALB}::test_color_full_chain_with_hue_saturation_gray"],
+    "stil_alb_blur": [f"{_ALB}::test_blur_reflect101_borders"],
+    "stil_alb_resize": [f"{_ALB}::test_resize_crop_flip_and_to_tensor"],
+    "stil_alb_rotate": [f"{_ALB}::test_rotate_quantised_reflect101"],
+    "stil_alb_to_tensor": [f"{_ALB}::test_resize_crop_flip_and_to_tensor"],
+    "stil_ring_enqueue": [f"{EP}::test_ring_enqueue_matches_python_ring", f"{EP}::test_ring_enqueue_rejects_bad_arguments_before_any_write"],
+    "stil_queue_mean": [f"{EP}::test_queue_mean_is_colsum_bit_for_bit_and_the_float64_mean", f"{EP}::test_queue_mean_clamps_the_count"],
+    "stil_rows_append": [f"{EP}::test_rows_append_matches_python_store",
+                         f"{EP}::test_auroc_reserved_store_equals_the_list_mode_and_raises_after_overflow"],
+}
+
+
+def _test_functions(filename):
+    """names of the module-level test functions of tests/<filename>, read with ast (the GPU modules are not imported)"""
+    with open(os.path.join(TESTS, filename)) as f:
+        tree = ast.parse(f.read())
+    return {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith("test_")}
+
+
+def test_every_entry_point_is_in_the_ledger():
+    from stil_tta_amd._lib import parse_header
+    header = set(parse_header())
+    assert header == set(LEDGER), f"not in the ledger: {sorted(header - set(LEDGER))}; not in the header: {sorted(set(LEDGER) - header)}"
+
+
+def test_every_named_test_exists():
+    cache = {}
+    for name, entry in LEDGER.items():
+        if isinstance(entry, str):
+            assert len(entry) > 20, f"{name}: a reason, not a shrug"
+            continue
+        assert entry, f"{name}: no test named"
+        for ref in entry:
+            fname, func = ref.split("::")
+            if fname not in cache:
+                cache[fname] = _test_functions(fname)
+            assert func in cache[fname], f"{name}: {ref} does not exist"
+
+
+def test_few_entry_points_go_without_a_test():
+    reasons = sorted(n for n, e in LEDGER.items() if isinstance(e, str))
+    assert len(reasons) <= MAX_REASONS, reasons
+
+
+def test_design_md_prints_this_ledger():
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        assert markdown_table() in f.read(), "DESIGN.md section 2: regenerate the table (python tests/test_abi_ledger_cpu.py)"
+
+
+def markdown_table():
+    rows = ["| entry point | direct test (tests/) or reason |", "|---|---|"]
+    for name, entry in LEDGER.items():
+        cell = f"none: {entry}" if isinstance(entry, str) else ", ".join(f"`{e}`" for e in entry)
+        rows.append(f"| `{name}` | {cell} |")
+    return "\n".join(rows)
+
+
+if __name__ == "__main__":
+    print(markdown_table())
