@@ -163,7 +163,8 @@ int stil_transpose(const float* in, float* out, int R, int C, void* stream);
 
 /* ---- BatchNorm2d (NHWC rows), ReLU, residual, max-pool: models/resnets.py:112-132,248-252 ----
  * stats: [4,C] = mean, rstd, a=gamma*rstd, beta (z = (x-mean)*a + beta); bn_eval_affine's ab: [3,C] = a, beta, running_mean.  Train forward also updates the running
- * statistics (momentum, unbiased variance) and num_batches_tracked. z = relu?(x*a + b + resid).
+ * statistics (momentum, unbiased variance) and num_batches_tracked; with running_mean, running_var and num_batches_tracked
+ * all NULL it leaves them out (the batch statistics still normalise: TENT's test-time forward, ops.frozen_bn_stats). z = relu?(x*a + b + resid).
  * `resid_stats` (optional, stil_bn_train_fwd_tiles): `resid` is the RAW conv output of the block's shortcut and resid_stats its
  * statistics block [4][C]; the shortcut's BatchNorm is applied inside this pass (the downsample branch never materialises its
  * normalised output, models/resnets.py:126-129).

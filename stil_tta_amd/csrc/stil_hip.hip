@@ -28,3 +28,4 @@ extern "C" int stil_device_count(void) {
 #include "augment_alb.hip"
 #include "layout.hip"
 #include "state.hip"
+#include "tta.hip"

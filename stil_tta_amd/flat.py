@@ -9,9 +9,10 @@ one RCCL all-reduce of the gradient slab.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -192,6 +193,69 @@ class FlatState:
         lib().adam_step(_p(self.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(self.chunk2tensor),
                         _p(self.steps), _p(self.active), len(self.tensors), self.total, float(lr), float(betas[0]),
                         float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _stream())
+
+
+class TentState:
+    """Test-time adaptation state over the flat slab (TENT, Wang et al., ICLR 2021; STiLModel.test_step): the adapted set A
+    (`names`, a subset of FlatState.names), its own gradient slab and Adam moments / step counts in the student slab's
+    layout (stil_adam_step with `active` = A), and the source values of A.  The training slabs (FlatState._grads,
+    exp_avg, exp_avg_sq, steps) are never written: during a step every parameter's gradient slot points into this
+    state's slab (`redirect`)."""
+
+    def __init__(self, flat: FlatState, names: List[str]):
+        self.flat = flat
+        ids = [flat.names.index(n) for n in names]
+        self.ids = ids
+        self.tensors = [flat.tensors[i] for i in ids]
+        dev = flat.params.device
+        self.grads = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.steps = torch.zeros(len(flat.tensors), dtype=torch.int32, device=dev)
+        act = torch.zeros(len(flat.tensors), dtype=torch.uint8)
+        act[ids] = 1
+        self.active = act.to(dev)
+        base = flat._grads.data_ptr()
+        self._slots = [self.grads[(t._gslot.data_ptr() - base) // 4:][:t.numel()].view(t.shape) for t in flat.tensors]
+        self.source: Optional[List[torch.Tensor]] = None
+
+    @torch.no_grad()
+    def snapshot(self):
+        self.source = [t.detach().clone() for t in self.tensors]
+
+    @torch.no_grad()
+    def restore(self):
+        """A <- its source values (no-op before the first snapshot)."""
+        if self.source is not None:
+            torch._foreach_copy_([t.data for t in self.tensors], self.source)
+
+    @torch.no_grad()
+    def clear_moments(self):
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.steps.zero_()
+
+    @contextlib.contextmanager
+    def redirect(self):
+        """Gradient slots -> this state's (zeroed) slab for the duration; slots, `_stil_touched` flags restored after."""
+        ts = self.flat.tensors
+        saved = [(t._gslot, t._stil_touched) for t in ts]
+        self.grads.zero_()
+        for t, s in zip(ts, self._slots):
+            t._gslot, t._stil_touched = s, False
+        try:
+            yield
+        finally:
+            join_side()
+            for t, (g, touched) in zip(ts, saved):
+                t._gslot, t._stil_touched = g, touched
+
+    @torch.no_grad()
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8):
+        f = self.flat
+        lib().adam_step(_p(f.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(f.chunk2tensor), _p(self.steps),
+                        _p(self.active), len(f.tensors), f.total, float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1.0,
+                        _stream())
 
 
 class StilAdam(torch.optim.Optimizer):

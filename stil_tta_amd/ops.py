@@ -611,6 +611,22 @@ def can_defer_bn(Cout: int) -> bool:
     return _BN_DEFER and _BN_EPILOGUE_STATS and Cout % 16 == 0 and Cout <= 2048
 
 
+_bn_frozen = False
+
+
+class frozen_bn_stats:
+    """with ops.frozen_bn_stats(): training-mode conv+BN layers normalise by the batch's own statistics and leave running_mean,
+    running_var and num_batches_tracked untouched (stil_bn_train_fwd(_tiles) with NULL running buffers) -- TENT's forward."""
+
+    def __enter__(self):
+        global _bn_frozen
+        self.prev, _bn_frozen = _bn_frozen, True
+
+    def __exit__(self, *exc):
+        global _bn_frozen
+        _bn_frozen = self.prev
+
+
 class ConvBnActFn(torch.autograd.Function):
     """z = relu?( BN_train(conv(x, w)) + residual? ) on NHWC activations.
 
@@ -678,6 +694,8 @@ class ConvBnActFn(torch.autograd.Function):
         assert fused or not defer, "deferred BatchNorm needs the epilogue statistics (can_defer_bn)"
         # deferred: no z.  Under parity tracing the tests still want this layer's ReLU decisions: z is materialised for them
         z = None if (defer and _trace is None) else torch.empty((M, Cout), dtype=torch.float32, device=dev)
+        if _bn_frozen:   # the batch statistics normalise as usual; the running buffers are left as they are
+            rmean = rvar = nbt = None
         if fused:
             nb = lib().bn_tiles_workspace_bytes(M, Cout, tile_rows)
             ws = _ws.get(nb, dev)
@@ -755,10 +773,12 @@ class ConvBnActFn(torch.autograd.Function):
         else:
             dres = None
         dx = None
+        # no weight-gradient product when the conv weight takes no gradient (test-time adaptation of the BatchNorm affines alone)
+        want_dw = ctx.needs_input_grad[1]
         if is_stem:
             Kp = stem[3]
             Kreal = w.shape[1] * k * k
-            dw = wgrad_param(w, dy, x, M, Cout, Kp, Kdst=Kreal)
+            dw = wgrad_param(w, dy, x, M, Cout, Kp, Kdst=Kreal) if want_dw else None
         else:
             _, H, W_, Cin = x.shape
             if ctx.needs_input_grad[0]:
@@ -799,7 +819,7 @@ class ConvBnActFn(torch.autograd.Function):
             elif gx_alias is not None:
                 dx = gx_alias
             gw = geom[:9]
-            dw = wgrad_param(w, dy, x, M, Cout, k * k * Cin, geom=gw, x_bn=xstats)
+            dw = wgrad_param(w, dy, x, M, Cout, k * k * Cin, geom=gw, x_bn=xstats) if want_dw else None
         return (dx, dw, (None if gslot is not None else dgamma), (None if bslot is not None else dbeta), None, None, None,
                 dres, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
@@ -1449,6 +1469,38 @@ class GegluFn(torch.autograd.Function):
         dh = torch.empty_like(h)
         lib().geglu_bwd(_p(g), _p(h), _p(dh), h.numel() // (2 * H), H, _stream())
         return dh
+
+
+class EntropyFn(torch.autograd.Function):
+    """TENT's loss (Wang et al., ICLR 2021): mean over rows of H(softmax(z)), H(p) = -sum_k p_k log p_k, for test-time
+    adaptation in STiLModel.test_step (STiLModel.py:523-524).  -> (loss, probabilities); the probabilities (no gradient)
+    are the scores the step reports, so no separate softmax launch runs.  One launch forms lse, p, the row entropies and
+    dZ / rows (stil_entropy_rows); backward scales dZ by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, z):
+        _chk(z)
+        R, K = z.shape
+        dev = z.device
+        lse = torch.empty((R,), dtype=torch.float64, device=dev)
+        p = torch.empty_like(z)
+        h = torch.empty((R,), dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lib().entropy_rows(_p(z), K, R, K, 1.0 / R, _p(lse), _p(p), K, _p(h), _p(dz), K, _p(loss), _stream())
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return _scale_by(dz, g)
+
+
+def entropy(z):
+    """-> (mean row entropy of softmax(z) [autograd], softmax(z) [no grad])"""
+    return EntropyFn.apply(z.contiguous())
 
 
 class RowSoftmaxFn(torch.autograd.Function):

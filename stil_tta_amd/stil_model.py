@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from . import ops
 from .metrics import AUROC, Accuracy
-from .flat import FlatState, StilAdam
+from .flat import FlatState, StilAdam, TentState
 from .modules import DisCoAttentionBackbone, TeacherPipe, fuse_mi_masks, random_mi_masks, set_teacher_pipe
 from .ops import _p, _stream
 from ._lib import lib
@@ -44,7 +44,14 @@ _DEFAULTS = dict(
     lr=3e-4, cosine_anneal_mult=1, dataset_length=1, check_val_every_n_epoch=1,  # only read by scheduler: cosine / linear
     global_contrast=False,  # data parallel: ITC / CLUB over the global batch (all-gather of embeddings)
     tabular_encoder="transformer",  # "saint": the STiLModel_SAINT.py variant (also selected by algorithm_name == "STiL_SAINT")
+    # test-time adaptation in test_step (the TODO of STiLModel.py:523-524): runs only when `tta` is truthy AND tta_method is set
+    tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021)
+    tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
+    tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
+    tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
 )
+_TTA_METHODS = (None, "tent")
+_TTA_PARAMS = ("bn", "norm")
 
 
 def _as_namespace(hp) -> SimpleNamespace:
@@ -156,6 +163,10 @@ class STiLModel(_Base):
         self.initialize_metrics(hp.batch_size, hp.batch_size)  # STiLModel.py:67,79: nclasses = hparams.batch_size
         self.best_val_score = 0
         self.flat: Optional[FlatState] = None
+        self._tent: Optional[TentState] = None
+        self.last_tta: Dict[str, torch.Tensor] = {}       # the latest adapted batch: loss, out_m, softmax(out_m)
+        self._check_tta(hp)
+        self.register_load_state_dict_post_hook(lambda *_: self._drop_tta())
         self._rng_offset = 0
         self.last: Dict[str, torch.Tensor] = {}
         if hp.checkpoint:
@@ -610,16 +621,111 @@ class STiLModel(_Base):
         for met in (self.acc_val, self.auc_val, self.acc_val_imaging, self.auc_val_imaging, self.acc_val_tabular, self.auc_val_tabular):
             met.reset()
 
-    @torch.no_grad()
     def test_step(self, batch, _=None):
-        """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores."""
+        """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
+        With `tta` and tta_method == "tent" the batch first adapts the model (TENT, _tent_step) and the scores are those of
+        the adapting forward."""
+        if self._tta_on():
+            return self._tent_step(batch)
+        with torch.no_grad():
+            x, y = batch
+            self.setup_device()
+            dev = self.prototypes.device
+            y_hat = self.model.forward((x[0].to(dev, torch.float32).contiguous(), x[1].to(dev, torch.float32).contiguous()), train=False)[0]
+            p = self._metric_probs(y_hat)
+            self.acc_test(p, y.to(dev))
+            self.auc_test(p, y.to(dev))
+            return p
+
+    # ------------------------------------------------------------------ test-time adaptation (TENT)
+    @staticmethod
+    def _check_tta(hp):
+        if hp.tta_method not in _TTA_METHODS:
+            raise ValueError(f"Unknown tta_method {hp.tta_method!r}: valid are {_TTA_METHODS}")
+        if hp.tta_params not in _TTA_PARAMS:
+            raise ValueError(f"Unknown tta_params {hp.tta_params!r}: valid are {_TTA_PARAMS}")
+        if hp.tta_method is not None and hp.tabular_encoder == "saint":
+            raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
+
+    def _tta_on(self) -> bool:
+        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method == "tent"
+
+    def tta_param_names(self):
+        """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
+        BNs included); with tta_params == "norm" also of every LayerNorm of model.encoder_tabular and model.transformer."""
+        groups = [("model.encoder_imaging", self.model.encoder_imaging, nn.BatchNorm2d)]
+        if self.hp.tta_params == "norm":
+            groups += [("model.encoder_tabular", self.model.encoder_tabular, nn.LayerNorm), ("model.transformer", self.model.transformer, nn.LayerNorm)]
+        out = []
+        for prefix, root, kind in groups:
+            for n, mod in root.named_modules():
+                if isinstance(mod, kind):
+                    out += [f"{prefix}.{n}.weight", f"{prefix}.{n}.bias"]
+        return out
+
+    def _drop_tta(self):
+        """Forget the adaptation state (moments, step counts, source values): load_state_dict calls this."""
+        self._tent = None
+
+    def reset_tta(self):
+        """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset_tta),
+        moments and step counts cleared; the next adapted batch takes the source values afresh."""
+        if self._tent is not None:
+            with torch.inference_mode(False):
+                self._tent.restore()
+                self._tent.clear_moments()
+                self._tent.source = None
+
+    def _tent_state(self) -> TentState:
+        if self._tent is None:
+            names = [n[len("model."):] for n in self.tta_param_names()]   # FlatState names the backbone's own parameters
+            self._tent = TentState(self.flat, names)
+        return self._tent
+
+    def _tent_step(self, batch):
+        """TENT (Wang et al., ICLR 2021) on one test batch: forward with batch-statistics BatchNorm (running buffers untouched,
+        no MI-layer dropout), loss = mean row entropy of softmax(out_m), gradients for A only (no weight-gradient products),
+        one Adam step over A (tta_lr, betas (0.9, 0.999), eps 1e-8, no weight decay).  The scores are softmax(out_m) of this
+        forward, before the update.  Rank-local: no collectives.  Works after freeze() and inside torch.inference_mode()."""
         x, y = batch
-        self.setup_device()
-        dev = self.prototypes.device
-        y_hat = self.model.forward((x[0].to(dev, torch.float32).contiguous(), x[1].to(dev, torch.float32).contiguous()), train=False)[0]
-        p = self._metric_probs(y_hat)
-        self.acc_test(p, y.to(dev))
-        self.auc_test(p, y.to(dev))
+        hp = self.hp
+        with torch.inference_mode(False):
+            self.setup_device()
+            dev = self.prototypes.device
+            x_img, x_tab = (t.to(dev, torch.float32).contiguous() for t in x[:2])
+            if x_img.is_inference():
+                x_img = x_img.clone()
+            if x_tab.is_inference():
+                x_tab = x_tab.clone()
+            st = self._tent_state()
+            if hp.tta_episodic:
+                if st.source is not None:
+                    st.restore()
+                st.clear_moments()
+            if st.source is None:
+                st.snapshot()
+            adapted = {id(t) for t in st.tensors}
+            flags = [(q, q.requires_grad) for q in self.parameters()]
+            exchange, ops._exchange = ops._exchange, None     # no gradient collectives: adaptation is per rank
+            try:
+                for q, _ in flags:
+                    q.requires_grad_(id(q) in adapted)
+                self.flat.refresh_layouts(student=True, teacher=False)
+                with torch.enable_grad(), st.redirect():
+                    with ops.frozen_bn_stats():
+                        out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+                    loss, probs = ops.entropy(out_m)
+                    loss.backward()
+                st.adam_step(hp.tta_lr)
+            finally:
+                ops._exchange = exchange
+                for q, f in flags:
+                    q.requires_grad_(f)
+            self.last_tta = dict(loss=loss.detach(), y_hat_m=out_m.detach(), probs=probs)
+            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
+            y = y.to(dev)
+            self.acc_test(p, y)
+            self.auc_test(p, y)
         return p
 
     def test_epoch_end(self, _=None):
