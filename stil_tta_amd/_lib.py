@@ -1,4 +1,4 @@
-"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h and include/stil_tta.h at import time.
+"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h, include/stil_tta.h and include/stil_eata.h at import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "stil_hip.h")
 TTA_HEADER = os.path.join(_ROOT, "include", "stil_tta.h")   # test-time adaptation (kept out of stil_hip.h's ledger)
+EATA_HEADER = os.path.join(_ROOT, "include", "stil_eata.h")  # EATA on top of TENT (a ledger of its own)
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -87,6 +88,7 @@ class _Lib:
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
         self.protos.update(parse_header(TTA_HEADER))
+        self.protos.update(parse_header(EATA_HEADER))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks
             fn.restype = restype

@@ -1,0 +1,256 @@
+// Test-time adaptation, EATA (Niu et al., ICML 2022, "Efficient Test-Time Model Adaptation without Forgetting") on top of
+// TENT (csrc/tta.hip): a reliable / non-redundant sample selection with per-sample weights, and a Fisher-weighted anchor
+// of the adapted set A to its source values.  Per row r of Z [rows, K], with m [K] the running mean of the selected
+// predictions (valid flag *m_valid), E0 = e_margin, d = d_margin, mu = momentum:
+//   lse_r, p_rk, H_r                as stil_entropy_rows (same code: bit-identical)
+//   c_r   = <m, p_r> / (max(|m|, 1e-8) max(|p_r|, 1e-8))     (m as it stood before the call; 0 while m is invalid)
+//   rel_r = H_r < E0 ; sel_r = rel_r and (m invalid or |c_r| < d) ; w_r = exp(E0 - H_r)
+//   n = sum sel, n_reliable = sum rel, L = (1/n) sum sel w H   (0 when n == 0)
+//   m' = pbar (m invalid) | mu m + (1 - mu) pbar, pbar = (1/n) sum sel p ; untouched when n == 0
+//   active_out[t] = active[t] and n > 0                        (the gate of the Adam step: n never leaves the device)
+//   dZ_rk = sel_r w_r (-p_rk (log p_rk + H_r)) grad_scale / n  (0 when n == 0)
+// Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
+// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (which reads the double lse and H of the first back).
+// The two slab kernels visit only the 1024-float chunks of A listed in `achunks` (checked against chunk2tensor / active as
+// stil_adam_step reads them); Fisher estimate and source values are compact: chunk j of them belongs to slab chunk achunks[j].
+
+// lse, softmax entropy (double) of one row by one 256-thread block: tta_entropy_rows_kernel's own sequence
+__device__ __forceinline__ void eata_row_lse_h(const float* __restrict__ zr, int K, float* red, double* redd, double& L, double& h) {
+  float mx = -INFINITY;
+  for (int k = threadIdx.x; k < K; k += 256) mx = fmaxf(mx, zr[k]);
+  mx = block_max(mx, red);
+  double s = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) s += exp((double)zr[k] - (double)mx);
+  s = tta_block_sum_d(s, redd);
+  L = (double)mx + log(s);
+  double a = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double lp = (double)zr[k] - L;
+    a -= exp(lp) * lp;
+  }
+  h = tta_block_sum_d(a, redd);
+}
+
+__global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict__ Z, int ld, int K, double e0, double dm,
+                                                         const float* __restrict__ m, const int* __restrict__ m_valid,
+                                                         double* __restrict__ lse, double* __restrict__ Hd,
+                                                         float* __restrict__ p, int ldp, float* __restrict__ H,
+                                                         float* __restrict__ c, float* __restrict__ w,
+                                                         unsigned char* __restrict__ rel, unsigned char* __restrict__ sel,
+                                                         int* __restrict__ counts) {
+  __shared__ float red[16];
+  __shared__ double redd[16];
+  const int r = blockIdx.x;
+  const float* zr = Z + (long)r * ld;
+  double L, h;
+  eata_row_lse_h(zr, K, red, redd, L, h);
+  const int valid = m_valid[0] != 0;
+  double mp = 0.0, mm = 0.0, pp = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double pk = exp((double)zr[k] - L);
+    p[(long)r * ldp + k] = (float)pk;
+    if (valid) {
+      const double mk = (double)m[k];
+      mp += mk * pk;
+      mm += mk * mk;
+    }
+    pp += pk * pk;
+  }
+  double cos = 0.0;
+  if (valid) {  // uniform across the block
+    mp = tta_block_sum_d(mp, redd);
+    mm = tta_block_sum_d(mm, redd);
+    pp = tta_block_sum_d(pp, redd);
+    cos = mp / (fmax(sqrt(mm), 1e-8) * fmax(sqrt(pp), 1e-8));
+  }
+  if (threadIdx.x == 0) {
+    const int is_rel = h < e0;
+    lse[r] = L;
+    Hd[r] = h;  // the dZ kernel reads the double H back: no second reduction
+    H[r] = (float)h;
+    c[r] = (float)cos;
+    w[r] = (float)exp(e0 - h);
+    rel[r] = (unsigned char)is_rel;
+    sel[r] = (unsigned char)(is_rel && (!valid || fabs(cos) < dm));
+    if (r == 0) counts[2] = valid;  // m's validity before this call: the reduce kernel's blocks read it while block 0 sets m_valid
+  }
+}
+
+// grid = cdiv(K, 256): every block counts n itself (rows bytes), block 0 writes the scalars and the gate
+__global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restrict__ p, int ldp, int rows, int K,
+                                                           const float* __restrict__ H, const float* __restrict__ w,
+                                                           const unsigned char* __restrict__ rel,
+                                                           const unsigned char* __restrict__ sel, double mu,
+                                                           float* __restrict__ m, int* __restrict__ m_valid,
+                                                           int* __restrict__ counts, float* __restrict__ loss,
+                                                           const unsigned char* __restrict__ active,
+                                                           unsigned char* __restrict__ active_out, int n_tensors) {
+  __shared__ double redd[16];
+  double nd = 0.0, nr = 0.0, ls = 0.0;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    if (sel[i]) {
+      nd += 1.0;
+      ls += (double)w[i] * (double)H[i];
+    }
+    if (rel[i]) nr += 1.0;
+  }
+  nd = tta_block_sum_d(nd, redd);  // integers below 2^53: exact
+  const int n = (int)nd;
+  const int valid = counts[2];
+  if (n > 0) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < K) {
+      double s = 0.0;
+      for (int r = 0; r < rows; ++r)
+        if (sel[r]) s += (double)p[(long)r * ldp + k];  // fixed order
+      s /= nd;
+      m[k] = (float)(valid ? mu * (double)m[k] + (1.0 - mu) * s : s);
+    }
+  }
+  if (blockIdx.x != 0) return;
+  nr = tta_block_sum_d(nr, redd);
+  ls = tta_block_sum_d(ls, redd);
+  if (threadIdx.x == 0) {
+    counts[0] = n;
+    counts[1] = (int)nr;
+    loss[0] = n > 0 ? (float)(ls / nd) : 0.f;
+    if (n > 0) m_valid[0] = 1;
+  }
+  for (int t = threadIdx.x; t < n_tensors; t += 256) active_out[t] = (unsigned char)(active[t] && n > 0);
+}
+
+__global__ __launch_bounds__(256) void eata_dz_kernel(const float* __restrict__ Z, int ld, int K, double e0, double gscale,
+                                                       const double* __restrict__ lse, const double* __restrict__ Hd,
+                                                       const unsigned char* __restrict__ sel, const int* __restrict__ counts,
+                                                       float* __restrict__ dZ, int ldd) {
+  const int r = blockIdx.x;
+  const int n = counts[0];
+  float* dr = dZ + (long)r * ldd;
+  if (n <= 0 || !sel[r]) {  // uniform across the block
+    for (int k = threadIdx.x; k < K; k += 256) dr[k] = 0.f;
+    return;
+  }
+  const float* zr = Z + (long)r * ld;
+  const double L = lse[r], h = Hd[r];  // the rows kernel's double lse and H of this row
+  const double f = exp(e0 - h) * gscale / (double)n;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double lp = (double)zr[k] - L;
+    dr[k] = (float)(-exp(lp) * (lp + h) * f);
+  }
+}
+
+extern "C" int stil_eata_rows(const float* Z, int ld, int rows, int K, float e_margin, float d_margin, float momentum,
+                              float grad_scale, float* m, int* m_valid, double* lse, double* Hd, float* p, int ldp, float* H,
+                              float* c, float* w, unsigned char* rel, unsigned char* sel, float* dZ, int ldd, int* counts, float* loss,
+                              const unsigned char* active, unsigned char* active_out, int n_tensors, void* stream) {
+  STIL_REQUIRE(Z && m && m_valid && lse && Hd && p && H && c && w && rel && sel && dZ && counts && loss, "stil_eata_rows: null pointer");
+  STIL_REQUIRE(rows >= 1 && K >= 1 && ld >= K, "stil_eata_rows: bad shape rows=%d K=%d ld=%d", rows, K, ld);
+  STIL_REQUIRE(ldp >= K && ldd >= K, "stil_eata_rows: ldp=%d ldd=%d < K=%d", ldp, ldd, K);
+  STIL_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (active && active_out)), "stil_eata_rows: n_tensors=%d needs both masks", n_tensors);
+  STIL_REQUIRE(momentum >= 0.f && momentum <= 1.f && d_margin >= 0.f, "stil_eata_rows: momentum=%g d_margin=%g", (double)momentum, (double)d_margin);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(eata_rows_kernel, dim3(rows), dim3(256), 0, s, Z, ld, K, (double)e_margin, (double)d_margin, (const float*)m,
+                     (const int*)m_valid, lse, Hd, p, ldp, H, c, w, rel, sel, counts);
+  STIL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(eata_reduce_kernel, dim3(cdiv(K, 256)), dim3(256), 0, s, (const float*)p, ldp, rows, K, (const float*)H,
+                     (const float*)w, (const unsigned char*)rel, (const unsigned char*)sel, (double)momentum, m, m_valid, counts,
+                     loss, active, active_out, n_tensors);
+  STIL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(eata_dz_kernel, dim3(rows), dim3(256), 0, s, Z, ld, K, (double)e_margin, (double)grad_scale,
+                     (const double*)lse, (const double*)Hd, (const unsigned char*)sel, (const int*)counts, dZ, ldd);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+// ---- the Fisher anchor and the Fisher accumulation: one block per listed chunk
+__device__ __forceinline__ bool eata_chunk_live(int ch, long nchunks, const int* __restrict__ chunk2tensor,
+                                                const unsigned char* __restrict__ active, int n_tensors) {
+  if (ch < 0 || ch >= nchunks) return false;
+  const int t = chunk2tensor[ch];
+  return t >= 0 && t < n_tensors && active[t];
+}
+
+__global__ __launch_bounds__(256) void eata_anchor_kernel(const float* __restrict__ params, const float* __restrict__ theta0,
+                                                           const float* __restrict__ fisher, float* __restrict__ grads,
+                                                           const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
+                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
+                                                           double alpha, double* __restrict__ partial) {
+  __shared__ double redd[16];
+  const int j = blockIdx.x, ch = achunks[j];
+  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
+    if (threadIdx.x == 0) partial[j] = 0.0;
+    return;
+  }
+  const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
+  const float4 th = reinterpret_cast<const float4*>(params)[i];
+  const float4 t0 = reinterpret_cast<const float4*>(theta0)[ic];
+  const float4 ff = reinterpret_cast<const float4*>(fisher)[ic];
+  float4 gg = reinterpret_cast<float4*>(grads)[i];
+  double s = 0.0;
+#define ANCHOR1(T, T0, F, G)                                      \
+  {                                                               \
+    const double d = (double)T - (double)T0, fd = (double)F * d;  \
+    s += fd * d;                                                  \
+    G = (float)((double)G + 2.0 * alpha * fd);                    \
+  }
+  ANCHOR1(th.x, t0.x, ff.x, gg.x) ANCHOR1(th.y, t0.y, ff.y, gg.y) ANCHOR1(th.z, t0.z, ff.z, gg.z) ANCHOR1(th.w, t0.w, ff.w, gg.w)
+#undef ANCHOR1
+  reinterpret_cast<float4*>(grads)[i] = gg;
+  s = tta_block_sum_d(s, redd);
+  if (threadIdx.x == 0) partial[j] = s;
+}
+
+__global__ __launch_bounds__(256) void eata_anchor_sum_kernel(const double* __restrict__ partial, int n, double alpha,
+                                                               float* __restrict__ R) {
+  __shared__ double redd[16];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = tta_block_sum_d(s, redd);
+  if (threadIdx.x == 0) R[0] = (float)(alpha * s);
+}
+
+__global__ __launch_bounds__(256) void eata_fisher_kernel(float* __restrict__ fisher, const float* __restrict__ grads,
+                                                           const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
+                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
+                                                           double scale) {
+  const int j = blockIdx.x, ch = achunks[j];
+  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
+  const float4 gg = reinterpret_cast<const float4*>(grads)[i];
+  float4 ff = reinterpret_cast<float4*>(fisher)[ic];
+  ff.x = (float)((double)ff.x + (double)gg.x * (double)gg.x * scale);
+  ff.y = (float)((double)ff.y + (double)gg.y * (double)gg.y * scale);
+  ff.z = (float)((double)ff.z + (double)gg.z * (double)gg.z * scale);
+  ff.w = (float)((double)ff.w + (double)gg.w * (double)gg.w * scale);
+  reinterpret_cast<float4*>(fisher)[ic] = ff;
+}
+
+extern "C" int stil_eata_anchor(const float* params, const float* theta0, const float* fisher, float* grads, const int* achunks,
+                                int n_achunks, const int* chunk2tensor, const unsigned char* active, int n_tensors, long n,
+                                float alpha, double* partial, float* R, void* stream) {
+  STIL_REQUIRE(params && theta0 && fisher && grads && achunks && chunk2tensor && active && partial && R, "stil_eata_anchor: null pointer");
+  STIL_REQUIRE(n >= 0 && n % 1024 == 0 && n_achunks >= 0 && n_tensors >= 0, "stil_eata_anchor: n=%ld must be a multiple of 1024, n_achunks=%d", n, n_achunks);
+  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0) && ((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0),
+               "stil_eata_anchor: slabs must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_achunks > 0) {
+    hipLaunchKernelGGL(eata_anchor_kernel, dim3(n_achunks), dim3(256), 0, s, params, theta0, fisher, grads, achunks, chunk2tensor,
+                       active, n_tensors, n / 1024, (double)alpha, partial);
+    STIL_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(eata_anchor_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, n_achunks, (double)alpha, R);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+extern "C" int stil_eata_fisher_accum(float* fisher, const float* grads, const int* achunks, int n_achunks, const int* chunk2tensor,
+                                      const unsigned char* active, int n_tensors, long n, float scale, void* stream) {
+  STIL_REQUIRE(fisher && grads && achunks && chunk2tensor && active, "stil_eata_fisher_accum: null pointer");
+  STIL_REQUIRE(n >= 0 && n % 1024 == 0 && n_achunks >= 0 && n_tensors >= 0, "stil_eata_fisher_accum: n=%ld must be a multiple of 1024, n_achunks=%d", n, n_achunks);
+  STIL_REQUIRE(((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0), "stil_eata_fisher_accum: slabs must be 16-byte aligned");
+  if (n_achunks == 0) return STIL_OK;
+  hipLaunchKernelGGL(eata_fisher_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, fisher, grads, achunks, chunk2tensor,
+                     active, n_tensors, n / 1024, (double)scale);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}

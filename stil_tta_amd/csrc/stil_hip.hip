@@ -29,3 +29,4 @@ extern "C" int stil_device_count(void) {
 #include "layout.hip"
 #include "state.hip"
 #include "tta.hip"
+#include "eata.hip"

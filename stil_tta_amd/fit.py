@@ -271,13 +271,21 @@ def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable
                 launch=step.launch if step is not None else None)
 
 
-def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Optional[int] = None) -> Dict[str, float]:
-    """Trainer.test(model, loader, ckpt_path=best) of trainers/evaluate.py:206-213 / trainers/test.py:85-90."""
+def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Optional[int] = None, tta_fisher_loader=None,
+         tta_fisher_batches: Optional[int] = None) -> Dict[str, float]:
+    """Trainer.test(model, loader, ckpt_path=best) of trainers/evaluate.py:206-213 / trainers/test.py:85-90.
+    tta_fisher_loader (tta_method "eata"): batches of source-like data in the test loader's layout; after the checkpoint load and
+    before the first test batch, model.estimate_tta_fisher takes EATA's Fisher estimate from (the first tta_fisher_batches of) it."""
     model.setup_device()
     if ckpt_path is not None:
         load_checkpoint(ckpt_path, model)
     model.freeze()
     dev = model.prototypes.device
+    if tta_fisher_loader is not None:
+        n = tta_fisher_batches
+        if n is None and hasattr(tta_fisher_loader, "__len__"):
+            n = len(tta_fisher_loader)
+        model.estimate_tta_fisher((_to_device(b, dev) for b in tta_fisher_loader), n)
     model.acc_test.reset()
     model.auc_test.reset()
     for i, batch in enumerate(test_loader):

@@ -10,6 +10,8 @@ All arithmetic runs in the HIP kernels of libstil_hip.so (ops.py); there is no C
 """
 from __future__ import annotations
 
+import contextlib
+import math
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -19,7 +21,7 @@ import torch.distributed as dist
 
 from . import ops
 from .metrics import AUROC, Accuracy
-from .flat import FlatState, StilAdam, TentState
+from .flat import EataState, FlatState, StilAdam, TentState
 from .modules import DisCoAttentionBackbone, TeacherPipe, fuse_mi_masks, random_mi_masks, set_teacher_pipe
 from .ops import _p, _stream
 from ._lib import lib
@@ -45,12 +47,17 @@ _DEFAULTS = dict(
     global_contrast=False,  # data parallel: ITC / CLUB over the global batch (all-gather of embeddings)
     tabular_encoder="transformer",  # "saint": the STiLModel_SAINT.py variant (also selected by algorithm_name == "STiL_SAINT")
     # test-time adaptation in test_step (the TODO of STiLModel.py:523-524): runs only when `tta` is truthy AND tta_method is set
-    tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021)
+    tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
+    # "eata" only: sample selection and the Fisher anchor
+    tta_e_margin=None,        # E0: rows with entropy below it are reliable; None = 0.4 ln(num_classes)
+    tta_d_margin=0.05,        # d: rows with |cos(running mean of selected predictions, p)| below it are non-redundant
+    tta_probs_momentum=0.9,   # momentum of that running mean
+    tta_fisher_alpha=2000.0,  # weight of the Fisher anchor (the paper's ImageNet value; its CIFAR runs use 1); inert without a Fisher estimate
 )
-_TTA_METHODS = (None, "tent")
+_TTA_METHODS = (None, "tent", "eata")
 _TTA_PARAMS = ("bn", "norm")
 
 
@@ -623,10 +630,10 @@ class STiLModel(_Base):
 
     def test_step(self, batch, _=None):
         """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
-        With `tta` and tta_method == "tent" the batch first adapts the model (TENT, _tent_step) and the scores are those of
-        the adapting forward."""
+        With `tta` and tta_method "tent" / "eata" the batch first adapts the model (_tent_step / _eata_step) and the scores
+        are those of the adapting forward."""
         if self._tta_on():
-            return self._tent_step(batch)
+            return self._eata_step(batch) if self.hp.tta_method == "eata" else self._tent_step(batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()
@@ -648,7 +655,7 @@ class STiLModel(_Base):
             raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
     def _tta_on(self) -> bool:
-        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method == "tent"
+        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method in ("tent", "eata")
 
     def tta_param_names(self):
         """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
@@ -664,22 +671,29 @@ class STiLModel(_Base):
         return out
 
     def _drop_tta(self):
-        """Forget the adaptation state (moments, step counts, source values): load_state_dict calls this."""
+        """Forget the adaptation state (moments, step counts, source values; EATA's running mean of predictions and its Fisher
+        estimate, which belongs to the weights it was estimated on): load_state_dict calls this."""
         self._tent = None
 
     def reset_tta(self):
         """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset_tta),
-        moments and step counts cleared; the next adapted batch takes the source values afresh."""
+        moments and step counts cleared; the next adapted batch takes the source values afresh.  EATA: the running mean of
+        the selected predictions is cleared too, the Fisher estimate is kept."""
         if self._tent is not None:
             with torch.inference_mode(False):
                 self._tent.restore()
                 self._tent.clear_moments()
                 self._tent.source = None
+                if isinstance(self._tent, EataState):
+                    self._tent.clear_probs()
 
     def _tent_state(self) -> TentState:
         if self._tent is None:
             names = [n[len("model."):] for n in self.tta_param_names()]   # FlatState names the backbone's own parameters
-            self._tent = TentState(self.flat, names)
+            if self.hp.tta_method == "eata":
+                self._tent = EataState(self.flat, names, self.hp.num_classes)
+            else:
+                self._tent = TentState(self.flat, names)
         return self._tent
 
     def _tent_step(self, batch):
@@ -692,11 +706,7 @@ class STiLModel(_Base):
         with torch.inference_mode(False):
             self.setup_device()
             dev = self.prototypes.device
-            x_img, x_tab = (t.to(dev, torch.float32).contiguous() for t in x[:2])
-            if x_img.is_inference():
-                x_img = x_img.clone()
-            if x_tab.is_inference():
-                x_tab = x_tab.clone()
+            x_img, x_tab = self._tta_inputs(x)
             st = self._tent_state()
             if hp.tta_episodic:
                 if st.source is not None:
@@ -704,12 +714,7 @@ class STiLModel(_Base):
                 st.clear_moments()
             if st.source is None:
                 st.snapshot()
-            adapted = {id(t) for t in st.tensors}
-            flags = [(q, q.requires_grad) for q in self.parameters()]
-            exchange, ops._exchange = ops._exchange, None     # no gradient collectives: adaptation is per rank
-            try:
-                for q, _ in flags:
-                    q.requires_grad_(id(q) in adapted)
+            with self._tta_scope(st):
                 self.flat.refresh_layouts(student=True, teacher=False)
                 with torch.enable_grad(), st.redirect():
                     with ops.frozen_bn_stats():
@@ -717,16 +722,153 @@ class STiLModel(_Base):
                     loss, probs = ops.entropy(out_m)
                     loss.backward()
                 st.adam_step(hp.tta_lr)
-            finally:
-                ops._exchange = exchange
-                for q, f in flags:
-                    q.requires_grad_(f)
             self.last_tta = dict(loss=loss.detach(), y_hat_m=out_m.detach(), probs=probs)
             p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
             y = y.to(dev)
             self.acc_test(p, y)
             self.auc_test(p, y)
         return p
+
+    # ------------------------------------------------------------------ shared by the TENT and EATA steps
+    @contextlib.contextmanager
+    def _tta_scope(self, st):
+        """requires_grad on A only, no gradient collectives (adaptation is per rank); flags and the exchange restored after"""
+        adapted = {id(t) for t in st.tensors}
+        flags = [(q, q.requires_grad) for q in self.parameters()]
+        exchange, ops._exchange = ops._exchange, None
+        try:
+            for q, _ in flags:
+                q.requires_grad_(id(q) in adapted)
+            yield
+        finally:
+            ops._exchange = exchange
+            for q, f in flags:
+                q.requires_grad_(f)
+
+    def _tta_inputs(self, x):
+        dev = self.prototypes.device
+        x_img, x_tab = (t.to(dev, torch.float32).contiguous() for t in x[:2])
+        if x_img.is_inference():
+            x_img = x_img.clone()
+        if x_tab.is_inference():
+            x_tab = x_tab.clone()
+        return x_img, x_tab
+
+    # ------------------------------------------------------------------ test-time adaptation (EATA)
+    def _eata_state(self) -> EataState:
+        if self.hp.tta_method != "eata":
+            raise ValueError(f"the Fisher estimate belongs to tta_method 'eata' (this model: {self.hp.tta_method!r})")
+        self.setup_device()
+        return self._tent_state()
+
+    def _eata_step(self, batch):
+        """EATA (Niu et al., ICML 2022) on one test batch: TENT's forward (batch-statistics BatchNorm, no MI-layer dropout) and
+        input-gradient-only backward, with (1) the loss restricted to the reliable (H_r < tta_e_margin) and non-redundant
+        (|cos(m, p_r)| < tta_d_margin, m = running mean of the selected predictions) rows, weighted by exp(E0 - H_r) and
+        averaged over the n selected rows, and (2) when a Fisher estimate is loaded, the anchor tta_fisher_alpha sum F (A - A0)^2
+        added to the loss and its gradient to A's.  One Adam step over A if and only if n > 0: n, the counts and that gate stay
+        on the device (stil_eata_rows writes the gated Adam mask), so the step reads nothing back.  The scores are softmax(out_m)
+        of this forward.  With tta_episodic, m is cleared and A restored before each batch: the redundancy filter and the
+        anchor are inert there (m is always invalid, A - A0 = 0)."""
+        x, y = batch
+        hp = self.hp
+        with torch.inference_mode(False):
+            self.setup_device()
+            dev = self.prototypes.device
+            x_img, x_tab = self._tta_inputs(x)
+            st = self._tent_state()
+            if hp.tta_episodic:
+                if st.source is not None:
+                    st.restore()
+                st.clear_moments()
+                st.clear_probs()
+            if st.source is None:
+                st.snapshot()
+            e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+            with self._tta_scope(st):
+                self.flat.refresh_layouts(student=True, teacher=False)
+                with torch.enable_grad(), st.redirect():
+                    with ops.frozen_bn_stats():
+                        out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+                    loss_ent, probs, info = ops.eata_entropy(out_m, e0, hp.tta_d_margin, hp.tta_probs_momentum, st.m, st.m_valid,
+                                                             st.active, st.gate)
+                    loss_ent.backward()
+                loss_anchor = torch.zeros((1,), dtype=torch.float32, device=dev)
+                if st.fisher is not None:
+                    st.anchor(hp.tta_fisher_alpha, loss_anchor)
+                st.gated_adam_step(hp.tta_lr)
+            loss_ent = loss_ent.detach()
+            self.last_tta = dict(loss=loss_ent + loss_anchor[0], y_hat_m=out_m.detach(), probs=probs, n_selected=info["counts"][0],
+                                 n_reliable=info["counts"][1], loss_entropy=loss_ent, loss_anchor=loss_anchor[0],
+                                 selected=info["sel"], reliable=info["rel"], entropy=info["H"], cos=info["cos"], weight=info["w"])
+            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
+            y = y.to(dev)
+            self.acc_test(p, y)
+            self.auc_test(p, y)
+        return p
+
+    def estimate_tta_fisher(self, batches, max_batches: Optional[int] = None):
+        """EATA's Fisher estimate of A at the CURRENT parameters (call it on the source model: before the first adapted batch
+        or after reset_tta()), from `batches` of source-like data laid out as test_step's (labels unused): per batch, the
+        forward of the adapting step, y_r = argmax_k out_m[r] (first maximum), l = mean_r CE(out_m[r], y_r), g = dl/dA;
+        F = (1/N) sum over the batches of g^2.  No parameter, BatchNorm buffer, teacher, prototype or training slab is written.
+        `batches` without a len() and no max_batches are materialised first (N scales every term)."""
+        with torch.inference_mode(False):
+            st = self._eata_state()
+            try:
+                N = len(batches)
+            except TypeError:
+                N = None
+            if max_batches is not None:
+                N = int(max_batches) if N is None else min(N, int(max_batches))
+            if N is None:
+                batches = list(batches)
+                N = len(batches)
+            if N < 1:
+                raise ValueError("estimate_tta_fisher needs at least one batch")
+            st.new_fisher()
+            dev = self.prototypes.device
+            seen = 0
+            with self._tta_scope(st):
+                for batch in batches:
+                    if seen >= N:
+                        break
+                    x_img, x_tab = self._tta_inputs(batch[0])
+                    self.flat.refresh_layouts(student=True, teacher=False)
+                    with torch.enable_grad(), st.redirect():
+                        with ops.frozen_bn_stats():
+                            out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+                        R, K = out_m.shape
+                        onehot = torch.empty((R, K), dtype=torch.float32, device=dev)
+                        mask = torch.empty((R,), dtype=torch.float32, device=dev)
+                        idx = torch.empty((R,), dtype=torch.int32, device=dev)
+                        lib().onehot_argmax(_p(out_m.detach()), R, K, 0.0, _p(onehot), _p(mask), _p(idx), _stream())
+                        ops.CEHardFn.apply(out_m, idx.long()).backward()
+                    st.fisher_accum(1.0 / N)
+                    seen += 1
+            if seen < N:  # an iterable shorter than max_batches: the mean is over the batches seen
+                if seen == 0:
+                    st.fisher = None
+                    raise ValueError("estimate_tta_fisher needs at least one batch")
+                st.fisher.mul_(N / seen)
+        return seen
+
+    def tta_fisher_state(self) -> Dict[str, torch.Tensor]:
+        """{state_dict name of a member of A: its Fisher estimate} (copies; {} when none is loaded).  Not part of state_dict(),
+        whose keys are the reference's."""
+        st = self._tent
+        if not isinstance(st, EataState) or st.fisher is None:
+            return {}
+        return dict(zip(self.tta_param_names(), st.fisher_tensors()))
+
+    def load_tta_fisher(self, fisher: Dict[str, torch.Tensor]):
+        """Load a Fisher estimate saved by tta_fisher_state(); the keys must be exactly tta_param_names()."""
+        names = self.tta_param_names()
+        if set(fisher.keys()) != set(names):
+            raise ValueError(f"Fisher estimate for {len(fisher)} tensors, the adapted set has {len(names)}: "
+                             f"missing {sorted(set(names) - set(fisher))[:3]}, unexpected {sorted(set(fisher) - set(names))[:3]}")
+        with torch.inference_mode(False):
+            self._eata_state().load_fisher([fisher[n] for n in names])
 
     def test_epoch_end(self, _=None):
         """STiLModel.py:535-543."""
