@@ -8,6 +8,7 @@ carries a `_gslot` view, so no ATen accumulate kernels run for the 406 parameter
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -627,6 +628,30 @@ class frozen_bn_stats:
         _bn_frozen = self.prev
 
 
+_bn_prior = None   # rho = B / (N + B) inside ops.bn_prior
+
+
+class bn_prior:
+    """with ops.frozen_bn_stats(), ops.bn_prior(N, B): the conv+BN layers normalise by N/(N+B) source + B/(N+B) batch statistics
+    (Schneider et al., NeurIPS 2020; source = running_mean / running_var, read-only; B = images in this batch, N >= 0 the
+    prior's pseudo-count) and their backward carries the batch statistics' share rho = B/(N+B) of the gradient
+    (stil_bn_prior_fwd(_tiles) / stil_bn_prior_bwd(_tiles), include/stil_bnprior.h).  Only meaningful under frozen_bn_stats."""
+
+    def __init__(self, N, B):
+        N, B = float(N), int(B)
+        if not (math.isfinite(N) and N >= 0.0) or B < 1:
+            raise ValueError(f"ops.bn_prior: N={N!r} must be finite and >= 0, B={B!r} >= 1")
+        self.rho = B / (N + B)
+
+    def __enter__(self):
+        global _bn_prior
+        self.prev, _bn_prior = _bn_prior, self.rho
+
+    def __exit__(self, *exc):
+        global _bn_prior
+        _bn_prior = self.prev
+
+
 class ConvBnActFn(torch.autograd.Function):
     """z = relu?( BN_train(conv(x, w)) + residual? ) on NHWC activations.
 
@@ -694,22 +719,37 @@ class ConvBnActFn(torch.autograd.Function):
         assert fused or not defer, "deferred BatchNorm needs the epilogue statistics (can_defer_bn)"
         # deferred: no z.  Under parity tracing the tests still want this layer's ReLU decisions: z is materialised for them
         z = None if (defer and _trace is None) else torch.empty((M, Cout), dtype=torch.float32, device=dev)
+        rho = delta = None
+        if _bn_prior is not None:   # source-statistics prior: the running buffers are read, never written
+            if not _bn_frozen or rmean is None or rvar is None:
+                raise RuntimeError("ops.bn_prior belongs inside ops.frozen_bn_stats and needs the layer's running statistics")
+            rho, delta = _bn_prior, torch.empty((Cout,), dtype=torch.float32, device=dev)
+            src_mean, src_var = rmean, rvar
         if _bn_frozen:   # the batch statistics normalise as usual; the running buffers are left as they are
             rmean = rvar = nbt = None
         if fused:
             nb = lib().bn_tiles_workspace_bytes(M, Cout, tile_rows)
             ws = _ws.get(nb, dev)
-            lib().bn_train_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(rstats), _p(z),
-                                     _p(stats), M, Cout, 1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
+            if rho is not None:
+                lib().bn_prior_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(rstats),
+                                         _p(z), _p(stats), _p(delta), M, Cout, 1 if relu else 0, 1e-5, _p(ws), nb, _stream())
+            else:
+                lib().bn_train_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(rstats), _p(z),
+                                         _p(stats), M, Cout, 1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
         else:
             assert rstats is None
             nb = lib().bn_workspace_bytes(M, Cout)
             ws = _ws.get(nb, dev)
-            lib().bn_train_fwd(_p(y), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(z), _p(stats), M, Cout,
-                               1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
+            if rho is not None:
+                lib().bn_prior_fwd(_p(y), _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(z), _p(stats), _p(delta), M, Cout,
+                                   1 if relu else 0, 1e-5, _p(ws), nb, _stream())
+            else:
+                lib().bn_train_fwd(_p(y), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(z), _p(stats), M, Cout,
+                                   1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
         if _trace is not None and relu:
             _trace["relu"][id(gamma)] = z.view(Nb, OH, OW, Cout)
-        ctx.save_for_backward(x, w, gamma, beta, y, None if defer else z, stats, xstats)
+        ctx.save_for_backward(x, w, gamma, beta, y, None if defer else z, stats, xstats, delta)
+        ctx.rho = rho
         ctx.cfg = (k, stride, pad, relu, stem is not None, resid is not None, geom, (Nb, OH, OW), stem)
         ctx.has_alias = bool(passthrough)
         ctx.premask_in = premask_in if (stem is None and stride == 1) else None     # only the plain / stride-1 gather dgrad GEMMs mask
@@ -734,7 +774,8 @@ class ConvBnActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gz, *more):
-        x, w, gamma, beta, y, z, stats, xstats = ctx.saved_tensors
+        x, w, gamma, beta, y, z, stats, xstats, delta = ctx.saved_tensors
+        rho = ctx.rho
         # outputs: (out[, x alias][, stats]) -- the alias gradient is the only other one that can carry a value
         gx_alias = more[0] if (len(more) and ctx.has_alias) else None
         k, stride, pad, relu, is_stem, has_res, geom, (Nb, OH, OW), stem = ctx.cfg
@@ -760,8 +801,15 @@ class ConvBnActFn(torch.autograd.Function):
             # the consumer's input-gradient GEMM left the per-tile sums: no reduction pass over gz and y
             nb2 = lib().bn_bwd_tiles_workspace_bytes(cell["nt"], Cout)
             ws2 = _ws.get(nb2 + 8, dev)
-            lib().bn_train_bwd_tiles(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(part), cell["nt"], _p(dy), _p(dgamma), _p(dbeta), _p(coef), M,
-                                     Cout, relu_mode, acc, _p(ws2), nb2, _stream())
+            if rho is not None:
+                lib().bn_prior_bwd_tiles(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(delta), rho, _p(part), cell["nt"], _p(dy), _p(dgamma),
+                                         _p(dbeta), _p(coef), M, Cout, relu_mode, acc, _p(ws2), nb2, _stream())
+            else:
+                lib().bn_train_bwd_tiles(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(part), cell["nt"], _p(dy), _p(dgamma), _p(dbeta), _p(coef), M,
+                                         Cout, relu_mode, acc, _p(ws2), nb2, _stream())
+        elif rho is not None:
+            lib().bn_prior_bwd(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(delta), rho, _p(dy), _p(gres), _p(dgamma), _p(dbeta), _p(coef), M,
+                               Cout, relu_mode, acc, _p(ws), nb, _stream())
         else:
             lib().bn_train_bwd(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(dy), _p(gres), _p(dgamma), _p(dbeta), _p(coef), M,
                                Cout, relu_mode, acc, _p(ws), nb, _stream())

@@ -48,16 +48,19 @@ _DEFAULTS = dict(
     tabular_encoder="transformer",  # "saint": the STiLModel_SAINT.py variant (also selected by algorithm_name == "STiL_SAINT")
     # test-time adaptation in test_step (the TODO of STiLModel.py:523-524): runs only when `tta` is truthy AND tta_method is set
     tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
+                         # | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
+    tta_bn_prior=None,   # N >= 0: the adapting forwards normalise by N/(N+B) source + B/(N+B) batch statistics (Schneider et al., NeurIPS 2020);
+                         # None: the batch statistics alone
     # "eata" only: sample selection and the Fisher anchor
     tta_e_margin=None,        # E0: rows with entropy below it are reliable; None = 0.4 ln(num_classes)
     tta_d_margin=0.05,        # d: rows with |cos(running mean of selected predictions, p)| below it are non-redundant
     tta_probs_momentum=0.9,   # momentum of that running mean
     tta_fisher_alpha=2000.0,  # weight of the Fisher anchor (the paper's ImageNet value; its CIFAR runs use 1); inert without a Fisher estimate
 )
-_TTA_METHODS = (None, "tent", "eata")
+_TTA_METHODS = (None, "tent", "eata", "bn_adapt")
 _TTA_PARAMS = ("bn", "norm")
 
 
@@ -631,9 +634,10 @@ class STiLModel(_Base):
     def test_step(self, batch, _=None):
         """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
         With `tta` and tta_method "tent" / "eata" the batch first adapts the model (_tent_step / _eata_step) and the scores
-        are those of the adapting forward."""
+        are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted."""
         if self._tta_on():
-            return self._eata_step(batch) if self.hp.tta_method == "eata" else self._tent_step(batch)
+            step = {"eata": self._eata_step, "bn_adapt": self._bn_adapt_step}.get(self.hp.tta_method, self._tent_step)
+            return step(batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()
@@ -651,11 +655,14 @@ class STiLModel(_Base):
             raise ValueError(f"Unknown tta_method {hp.tta_method!r}: valid are {_TTA_METHODS}")
         if hp.tta_params not in _TTA_PARAMS:
             raise ValueError(f"Unknown tta_params {hp.tta_params!r}: valid are {_TTA_PARAMS}")
+        N = hp.tta_bn_prior
+        if N is not None and (isinstance(N, bool) or not isinstance(N, (int, float)) or not math.isfinite(N) or N < 0):
+            raise ValueError(f"tta_bn_prior must be None or a finite number >= 0, not {N!r}")
         if hp.tta_method is not None and hp.tabular_encoder == "saint":
             raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
     def _tta_on(self) -> bool:
-        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method in ("tent", "eata")
+        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method in ("tent", "eata", "bn_adapt")
 
     def tta_param_names(self):
         """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
@@ -717,7 +724,7 @@ class STiLModel(_Base):
             with self._tta_scope(st):
                 self.flat.refresh_layouts(student=True, teacher=False)
                 with torch.enable_grad(), st.redirect():
-                    with ops.frozen_bn_stats():
+                    with self._tta_bn_scope(x_img.shape[0]):
                         out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
                     loss, probs = ops.entropy(out_m)
                     loss.backward()
@@ -729,7 +736,39 @@ class STiLModel(_Base):
             self.auc_test(p, y)
         return p
 
+    def _bn_adapt_step(self, batch):
+        """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the adapting forward of _tent_step (BatchNorm
+        statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
+        No adapted set, no gradient, no optimiser, no state: reset_tta() and tta_episodic have nothing to act on."""
+        x, y = batch
+        hp = self.hp
+        with torch.inference_mode(False), torch.no_grad():
+            self.setup_device()
+            dev = self.prototypes.device
+            x_img, x_tab = self._tta_inputs(x)
+            self.flat.refresh_layouts(student=True, teacher=False)
+            with self._tta_bn_scope(x_img.shape[0]):
+                out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+            probs = ops.softmax_rows(out_m)
+            self.last_tta = dict(y_hat_m=out_m, probs=probs)
+            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
+            y = y.to(dev)
+            self.acc_test(p, y)
+            self.auc_test(p, y)
+        return p
+
     # ------------------------------------------------------------------ shared by the TENT and EATA steps
+    @contextlib.contextmanager
+    def _tta_bn_scope(self, B):
+        """the BatchNorm of an adapting forward over B images: batch statistics, running buffers untouched; with tta_bn_prior = N
+        blended with the source statistics at rho = B / (N + B) (a short last batch gets its own rho)"""
+        with ops.frozen_bn_stats():
+            if self.hp.tta_bn_prior is None:
+                yield
+            else:
+                with ops.bn_prior(self.hp.tta_bn_prior, B):
+                    yield
+
     @contextlib.contextmanager
     def _tta_scope(self, st):
         """requires_grad on A only, no gradient collectives (adaptation is per rank); flags and the exchange restored after"""
@@ -788,7 +827,7 @@ class STiLModel(_Base):
             with self._tta_scope(st):
                 self.flat.refresh_layouts(student=True, teacher=False)
                 with torch.enable_grad(), st.redirect():
-                    with ops.frozen_bn_stats():
+                    with self._tta_bn_scope(x_img.shape[0]):
                         out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
                     loss_ent, probs, info = ops.eata_entropy(out_m, e0, hp.tta_d_margin, hp.tta_probs_momentum, st.m, st.m_valid,
                                                              st.active, st.gate)
@@ -836,7 +875,7 @@ class STiLModel(_Base):
                     x_img, x_tab = self._tta_inputs(batch[0])
                     self.flat.refresh_layouts(student=True, teacher=False)
                     with torch.enable_grad(), st.redirect():
-                        with ops.frozen_bn_stats():
+                        with self._tta_bn_scope(x_img.shape[0]):
                             out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
                         R, K = out_m.shape
                         onehot = torch.empty((R, K), dtype=torch.float32, device=dev)
