@@ -57,6 +57,18 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   for (int i = 0; i < nw; ++i) r += sh[i];  // fixed order: deterministic
   return r;
 }
+// The same in double (`sh`: >= 16 doubles): the log-sum-exps of the CLIP loss (loss.hip) and of test-time adaptation (tta.hip).
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if (l == 0) sh[w] = v;
+  __syncthreads();
+  double r = 0.0;
+  for (int i = 0; i < nw; ++i) r += sh[i];  // fixed order: deterministic
+  return r;
+}
 __device__ __forceinline__ float block_max(float v, float* sh) {
   v = wave_max(v);
   int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;

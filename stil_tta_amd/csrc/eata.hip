@@ -2,7 +2,7 @@
 // TENT (csrc/tta.hip): a reliable / non-redundant sample selection with per-sample weights, and a Fisher-weighted anchor
 // of the adapted set A to its source values.  Per row r of Z [rows, K], with m [K] the running mean of the selected
 // predictions (valid flag *m_valid), E0 = e_margin, d = d_margin, mu = momentum:
-//   lse_r, p_rk, H_r                as stil_entropy_rows (same code: bit-identical)
+//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta.hip: bit-identical)
 //   c_r   = <m, p_r> / (max(|m|, 1e-8) max(|p_r|, 1e-8))     (m as it stood before the call; 0 while m is invalid)
 //   rel_r = H_r < E0 ; sel_r = rel_r and (m invalid or |c_r| < d) ; w_r = exp(E0 - H_r)
 //   n = sum sel, n_reliable = sum rel, L = (1/n) sum sel w H   (0 when n == 0)
@@ -13,23 +13,6 @@
 // partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (which reads the double lse and H of the first back).
 // The two slab kernels visit only the 1024-float chunks of A listed in `achunks` (checked against chunk2tensor / active as
 // stil_adam_step reads them); Fisher estimate and source values are compact: chunk j of them belongs to slab chunk achunks[j].
-
-// lse, softmax entropy (double) of one row by one 256-thread block: tta_entropy_rows_kernel's own sequence
-__device__ __forceinline__ void eata_row_lse_h(const float* __restrict__ zr, int K, float* red, double* redd, double& L, double& h) {
-  float mx = -INFINITY;
-  for (int k = threadIdx.x; k < K; k += 256) mx = fmaxf(mx, zr[k]);
-  mx = block_max(mx, red);
-  double s = 0.0;
-  for (int k = threadIdx.x; k < K; k += 256) s += exp((double)zr[k] - (double)mx);
-  s = tta_block_sum_d(s, redd);
-  L = (double)mx + log(s);
-  double a = 0.0;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const double lp = (double)zr[k] - L;
-    a -= exp(lp) * lp;
-  }
-  h = tta_block_sum_d(a, redd);
-}
 
 __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict__ Z, int ld, int K, double e0, double dm,
                                                          const float* __restrict__ m, const int* __restrict__ m_valid,
@@ -43,7 +26,7 @@ __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict_
   const int r = blockIdx.x;
   const float* zr = Z + (long)r * ld;
   double L, h;
-  eata_row_lse_h(zr, K, red, redd, L, h);
+  tta_row_lse_h(zr, K, red, redd, L, h);
   const int valid = m_valid[0] != 0;
   double mp = 0.0, mm = 0.0, pp = 0.0;
   for (int k = threadIdx.x; k < K; k += 256) {
@@ -58,9 +41,9 @@ __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict_
   }
   double cos = 0.0;
   if (valid) {  // uniform across the block
-    mp = tta_block_sum_d(mp, redd);
-    mm = tta_block_sum_d(mm, redd);
-    pp = tta_block_sum_d(pp, redd);
+    mp = block_sum_d(mp, redd);
+    mm = block_sum_d(mm, redd);
+    pp = block_sum_d(pp, redd);
     cos = mp / (fmax(sqrt(mm), 1e-8) * fmax(sqrt(pp), 1e-8));
   }
   if (threadIdx.x == 0) {
@@ -94,7 +77,7 @@ __global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restric
     }
     if (rel[i]) nr += 1.0;
   }
-  nd = tta_block_sum_d(nd, redd);  // integers below 2^53: exact
+  nd = block_sum_d(nd, redd);  // integers below 2^53: exact
   const int n = (int)nd;
   const int valid = counts[2];
   if (n > 0) {
@@ -108,8 +91,8 @@ __global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restric
     }
   }
   if (blockIdx.x != 0) return;
-  nr = tta_block_sum_d(nr, redd);
-  ls = tta_block_sum_d(ls, redd);
+  nr = block_sum_d(nr, redd);
+  ls = block_sum_d(ls, redd);
   if (threadIdx.x == 0) {
     counts[0] = n;
     counts[1] = (int)nr;
@@ -196,7 +179,7 @@ __global__ __launch_bounds__(256) void eata_anchor_kernel(const float* __restric
   ANCHOR1(th.x, t0.x, ff.x, gg.x) ANCHOR1(th.y, t0.y, ff.y, gg.y) ANCHOR1(th.z, t0.z, ff.z, gg.z) ANCHOR1(th.w, t0.w, ff.w, gg.w)
 #undef ANCHOR1
   reinterpret_cast<float4*>(grads)[i] = gg;
-  s = tta_block_sum_d(s, redd);
+  s = block_sum_d(s, redd);
   if (threadIdx.x == 0) partial[j] = s;
 }
 
@@ -205,7 +188,7 @@ __global__ __launch_bounds__(256) void eata_anchor_sum_kernel(const double* __re
   __shared__ double redd[16];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = tta_block_sum_d(s, redd);
+  s = block_sum_d(s, redd);
   if (threadIdx.x == 0) R[0] = (float)(alpha * s);
 }
 

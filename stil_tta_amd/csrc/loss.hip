@@ -110,17 +110,6 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 // gradient (15x what ATen's fp32 path leaves there; tests/tools/itc_ladder.py, itc_noise.py, round-5 experiment log).  The
 // log-sum-exps and the probabilities are therefore formed in double and dZ is rounded ONCE: its error is the half-ulp of the
 // fp32 it is stored in (zero-mean, independent per element).  B^2 double exponentials: 65 k at B = 256, noise beside the step.
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  double r = 0.0;
-  for (int i = 0; i < nw; ++i) r += sh[i];  // fixed order: deterministic
-  return r;
-}
 __global__ __launch_bounds__(256) void lse_rows_kernel(const float* __restrict__ Z, double* __restrict__ lse, int R, int C) {
   __shared__ float red[16];
   __shared__ double redd[16];

@@ -10,16 +10,22 @@
 // __shfl_xor trees and a fixed-order sum of the four wave partials, so the result is bit-identical on repetition.
 #include "common.h"
 
-__device__ __forceinline__ double tta_block_sum_d(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  double r = 0.0;
-  for (int i = 0; i < nw; ++i) r += sh[i];  // fixed order: deterministic
-  return r;
+// lse and softmax entropy (double) of one row zr[0:K] by one 256-thread block: shared by stil_entropy_rows and stil_eata_rows,
+// whose lse, p and H are therefore bit-identical
+__device__ __forceinline__ void tta_row_lse_h(const float* __restrict__ zr, int K, float* red, double* redd, double& L, double& h) {
+  float m = -INFINITY;
+  for (int k = threadIdx.x; k < K; k += 256) m = fmaxf(m, zr[k]);
+  m = block_max(m, red);
+  double s = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) s += exp((double)zr[k] - (double)m);
+  s = block_sum_d(s, redd);
+  L = (double)m + log(s);
+  double a = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double lp = (double)zr[k] - L;
+    a -= exp(lp) * lp;
+  }
+  h = block_sum_d(a, redd);
 }
 
 __global__ __launch_bounds__(256) void tta_entropy_rows_kernel(const float* __restrict__ Z, int ld, int K, double gscale,
@@ -29,19 +35,8 @@ __global__ __launch_bounds__(256) void tta_entropy_rows_kernel(const float* __re
   __shared__ double redd[16];
   const int r = blockIdx.x;
   const float* zr = Z + (long)r * ld;
-  float m = -INFINITY;
-  for (int k = threadIdx.x; k < K; k += 256) m = fmaxf(m, zr[k]);
-  m = block_max(m, red);
-  double s = 0.0;
-  for (int k = threadIdx.x; k < K; k += 256) s += exp((double)zr[k] - (double)m);
-  s = tta_block_sum_d(s, redd);
-  const double L = (double)m + log(s);
-  double h = 0.0;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const double lp = (double)zr[k] - L;
-    h -= exp(lp) * lp;
-  }
-  h = tta_block_sum_d(h, redd);
+  double L, h;
+  tta_row_lse_h(zr, K, red, redd, L, h);
   if (threadIdx.x == 0) {
     lse[r] = L;
     H[r] = (float)h;
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(256) void tta_entropy_mean_kernel(const float* __re
   __shared__ double redd[16];
   double s = 0.0;
   for (int i = threadIdx.x; i < rows; i += 256) s += (double)H[i];
-  s = tta_block_sum_d(s, redd);
+  s = block_sum_d(s, redd);
   if (threadIdx.x == 0) mean[0] = (float)(s / (double)rows);
 }
 

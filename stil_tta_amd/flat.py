@@ -9,10 +9,9 @@ one RCCL all-reduce of the gradient slab.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
 import os
-from typing import List, Optional, Tuple
+from typing import List, Tuple
 
 import torch
 import torch.nn as nn
@@ -193,148 +192,6 @@ class FlatState:
         lib().adam_step(_p(self.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(self.chunk2tensor),
                         _p(self.steps), _p(self.active), len(self.tensors), self.total, float(lr), float(betas[0]),
                         float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _stream())
-
-
-class TentState:
-    """Test-time adaptation state over the flat slab (TENT, Wang et al., ICLR 2021; STiLModel.test_step): the adapted set A
-    (`names`, a subset of FlatState.names), its own gradient slab and Adam moments / step counts in the student slab's
-    layout (stil_adam_step with `active` = A), and the source values of A.  The training slabs (FlatState._grads,
-    exp_avg, exp_avg_sq, steps) are never written: during a step every parameter's gradient slot points into this
-    state's slab (`redirect`)."""
-
-    def __init__(self, flat: FlatState, names: List[str]):
-        self.flat = flat
-        ids = [flat.names.index(n) for n in names]
-        self.ids = ids
-        self.tensors = [flat.tensors[i] for i in ids]
-        dev = flat.params.device
-        self.grads = torch.zeros(flat.total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(flat.total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(flat.total, dtype=torch.float32, device=dev)
-        self.steps = torch.zeros(len(flat.tensors), dtype=torch.int32, device=dev)
-        act = torch.zeros(len(flat.tensors), dtype=torch.uint8)
-        act[ids] = 1
-        self.active = act.to(dev)
-        base = flat._grads.data_ptr()
-        self._slots = [self.grads[(t._gslot.data_ptr() - base) // 4:][:t.numel()].view(t.shape) for t in flat.tensors]
-        self.source: Optional[List[torch.Tensor]] = None
-
-    @torch.no_grad()
-    def snapshot(self):
-        self.source = [t.detach().clone() for t in self.tensors]
-
-    @torch.no_grad()
-    def restore(self):
-        """A <- its source values (no-op before the first snapshot)."""
-        if self.source is not None:
-            torch._foreach_copy_([t.data for t in self.tensors], self.source)
-
-    @torch.no_grad()
-    def clear_moments(self):
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        self.steps.zero_()
-
-    @contextlib.contextmanager
-    def redirect(self):
-        """Gradient slots -> this state's (zeroed) slab for the duration; slots, `_stil_touched` flags restored after."""
-        ts = self.flat.tensors
-        saved = [(t._gslot, t._stil_touched) for t in ts]
-        self.grads.zero_()
-        for t, s in zip(ts, self._slots):
-            t._gslot, t._stil_touched = s, False
-        try:
-            yield
-        finally:
-            join_side()
-            for t, (g, touched) in zip(ts, saved):
-                t._gslot, t._stil_touched = g, touched
-
-    @torch.no_grad()
-    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8):
-        f = self.flat
-        lib().adam_step(_p(f.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(f.chunk2tensor), _p(self.steps),
-                        _p(self.active), len(f.tensors), f.total, float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1.0,
-                        _stream())
-
-
-class EataState(TentState):
-    """TentState plus what EATA adds (Niu et al., ICML 2022): the running mean `m` [K] of the selected predictions and its
-    validity flag, the gated copy of the Adam mask (`gate` = active and n > 0, written by stil_eata_rows), and the Fisher
-    estimate.  Fisher and source values are COMPACT: `achunks` lists the 1024-float slab chunks of A, chunk j of `fisher` /
-    `theta0` belongs to slab chunk achunks[j] (`source` holds views into `theta0`, so restore() is TentState's).  For A =
-    the 106 BatchNorm affines of a ResNet-50 that is 114 chunks: 456 KiB each, against 178 MiB for a slab in the flat layout."""
-
-    def __init__(self, flat: FlatState, names: List[str], num_classes: int):
-        super().__init__(flat, names)
-        dev = flat.params.device
-        base = flat.params.data_ptr()
-        chunks, self._spans = [], []
-        for t in self.tensors:
-            o = (t.data_ptr() - base) // 4
-            self._spans.append((len(chunks) * ALIGN, t.numel()))
-            chunks += list(range(o // ALIGN, (o + _round_up(t.numel())) // ALIGN))
-        self.n_achunks = len(chunks)
-        self.achunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        self.theta0 = torch.zeros(self.n_achunks * ALIGN, dtype=torch.float32, device=dev)
-        self.fisher: Optional[torch.Tensor] = None
-        self.partial = torch.zeros(max(self.n_achunks, 1), dtype=torch.float64, device=dev)
-        self.m = torch.zeros(num_classes, dtype=torch.float32, device=dev)
-        self.m_valid = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.gate = torch.zeros_like(self.active)
-
-    def _compact_views(self, buf):
-        return [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._spans, self.tensors)]
-
-    @torch.no_grad()
-    def snapshot(self):
-        self.source = self._compact_views(self.theta0)
-        torch._foreach_copy_(self.source, [t.detach() for t in self.tensors])
-
-    @torch.no_grad()
-    def clear_probs(self):
-        self.m.zero_()
-        self.m_valid.zero_()
-
-    # ---- Fisher estimate: one tensor per member of A <-> the compact slab
-    @torch.no_grad()
-    def new_fisher(self):
-        self.fisher = torch.zeros_like(self.theta0)
-
-    @torch.no_grad()
-    def fisher_accum(self, scale: float):
-        """fisher += grads^2 * scale over A's chunks of this state's gradient slab"""
-        f = self.flat
-        lib().eata_fisher_accum(_p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks, _p(f.chunk2tensor),
-                                _p(self.active), len(f.tensors), f.total, float(scale), _stream())
-
-    @torch.no_grad()
-    def anchor(self, alpha: float, out: torch.Tensor):
-        """grads += 2 alpha F (theta - theta0) over A's chunks; out[0] = alpha sum F (theta - theta0)^2"""
-        f = self.flat
-        lib().eata_anchor(_p(f.params), _p(self.theta0), _p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks,
-                          _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total, float(alpha), _p(self.partial), _p(out),
-                          _stream())
-
-    def fisher_tensors(self) -> List[torch.Tensor]:
-        return [v.clone() for v in self._compact_views(self.fisher)]
-
-    @torch.no_grad()
-    def load_fisher(self, tensors: List[torch.Tensor]):
-        self.new_fisher()
-        views = self._compact_views(self.fisher)
-        for v, t in zip(views, tensors):
-            if tuple(v.shape) != tuple(t.shape):
-                raise ValueError(f"Fisher estimate of shape {tuple(t.shape)} for a parameter of shape {tuple(v.shape)}")
-        torch._foreach_copy_(views, [t.detach().to(self.fisher.device, torch.float32) for t in tensors])
-
-    @torch.no_grad()
-    def gated_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8):
-        """TentState.adam_step under `gate`: with n == 0 neither A, nor its moments, nor its step counts move."""
-        f = self.flat
-        lib().adam_step(_p(f.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(f.chunk2tensor), _p(self.steps),
-                        _p(self.gate), len(f.tensors), f.total, float(lr), float(betas[0]), float(betas[1]), float(eps), 0.0, 1.0,
-                        _stream())
 
 
 class StilAdam(torch.optim.Optimizer):

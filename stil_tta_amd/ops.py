@@ -1519,78 +1519,6 @@ class GegluFn(torch.autograd.Function):
         return dh
 
 
-class EntropyFn(torch.autograd.Function):
-    """TENT's loss (Wang et al., ICLR 2021): mean over rows of H(softmax(z)), H(p) = -sum_k p_k log p_k, for test-time
-    adaptation in STiLModel.test_step (STiLModel.py:523-524).  -> (loss, probabilities); the probabilities (no gradient)
-    are the scores the step reports, so no separate softmax launch runs.  One launch forms lse, p, the row entropies and
-    dZ / rows (stil_entropy_rows); backward scales dZ by the incoming gradient."""
-
-    @staticmethod
-    def forward(ctx, z):
-        _chk(z)
-        R, K = z.shape
-        dev = z.device
-        lse = torch.empty((R,), dtype=torch.float64, device=dev)
-        p = torch.empty_like(z)
-        h = torch.empty((R,), dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        lib().entropy_rows(_p(z), K, R, K, 1.0 / R, _p(lse), _p(p), K, _p(h), _p(dz), K, _p(loss), _stream())
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return loss, p
-
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return _scale_by(dz, g)
-
-
-def entropy(z):
-    """-> (mean row entropy of softmax(z) [autograd], softmax(z) [no grad])"""
-    return EntropyFn.apply(z.contiguous())
-
-
-class EataEntropyFn(torch.autograd.Function):
-    """EATA's loss (Niu et al., ICML 2022) beside EntropyFn: (1/n) sum over the selected rows of w_r H_r, the selection
-    (reliable: H_r < e_margin; non-redundant: |cos(m, p_r)| < d_margin), the weights w_r = exp(e_margin - H_r), the update of
-    the running mean m and the gate of the Adam step, all in stil_eata_rows: n stays on the device.
-    -> (loss, probabilities, info); info = dict(H, cos, w, rel, sel, counts [n, n_reliable, m valid before, -], lse).
-    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient; w carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, z, e_margin, d_margin, momentum, m, m_valid, active, gate, info):
-        _chk(z, m, m_valid, active, gate)
-        R, K = z.shape
-        dev = z.device
-        lse, hd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
-        p = torch.empty_like(z)
-        h, c, w = (torch.empty((R,), dtype=torch.float32, device=dev) for _ in range(3))
-        rel, sel = (torch.empty((R,), dtype=torch.uint8, device=dev) for _ in range(2))
-        dz = torch.empty_like(z)
-        counts = torch.zeros((4,), dtype=torch.int32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        nt = 0 if active is None else active.numel()
-        lib().eata_rows(_p(z), K, R, K, float(e_margin), float(d_margin), float(momentum), 1.0, _p(m), _p(m_valid), _p(lse), _p(hd), _p(p), K,
-                        _p(h), _p(c), _p(w), _p(rel), _p(sel), _p(dz), K, _p(counts), _p(loss), _p(active), _p(gate), nt, _stream())
-        info.update(H=h, cos=c, w=w, rel=rel, sel=sel, counts=counts, lse=lse)
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return loss, p
-
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return (_scale_by(dz, g),) + (None,) * 8
-
-
-def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=None):
-    """-> (EATA's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates m / m_valid / gate."""
-    info = {}
-    loss, p = EataEntropyFn.apply(z.contiguous(), e_margin, d_margin, momentum, m, m_valid, active, gate, info)
-    return loss, p, info
-
-
 class RowSoftmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z):

@@ -10,8 +10,6 @@ All arithmetic runs in the HIP kernels of libstil_hip.so (ops.py); there is no C
 """
 from __future__ import annotations
 
-import contextlib
-import math
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -19,9 +17,9 @@ import torch
 import torch.nn as nn
 import torch.distributed as dist
 
-from . import ops
+from . import ops, tta
 from .metrics import AUROC, Accuracy
-from .flat import EataState, FlatState, StilAdam, TentState
+from .flat import FlatState, StilAdam
 from .modules import DisCoAttentionBackbone, TeacherPipe, fuse_mi_masks, random_mi_masks, set_teacher_pipe
 from .ops import _p, _stream
 from ._lib import lib
@@ -60,8 +58,6 @@ _DEFAULTS = dict(
     tta_probs_momentum=0.9,   # momentum of that running mean
     tta_fisher_alpha=2000.0,  # weight of the Fisher anchor (the paper's ImageNet value; its CIFAR runs use 1); inert without a Fisher estimate
 )
-_TTA_METHODS = (None, "tent", "eata", "bn_adapt")
-_TTA_PARAMS = ("bn", "norm")
 
 
 def _as_namespace(hp) -> SimpleNamespace:
@@ -173,10 +169,10 @@ class STiLModel(_Base):
         self.initialize_metrics(hp.batch_size, hp.batch_size)  # STiLModel.py:67,79: nclasses = hparams.batch_size
         self.best_val_score = 0
         self.flat: Optional[FlatState] = None
-        self._tent: Optional[TentState] = None
+        self._tent: Optional[tta.TentState] = None        # the adaptation state (tta.py): created by the first adapted batch / Fisher estimate
         self.last_tta: Dict[str, torch.Tensor] = {}       # the latest adapted batch: loss, out_m, softmax(out_m)
-        self._check_tta(hp)
-        self.register_load_state_dict_post_hook(lambda *_: self._drop_tta())
+        tta.check_hparams(hp)
+        self.register_load_state_dict_post_hook(lambda *_: tta.drop(self))
         self._rng_offset = 0
         self.last: Dict[str, torch.Tensor] = {}
         if hp.checkpoint:
@@ -231,8 +227,10 @@ class STiLModel(_Base):
 
     def _metric_probs(self, logits):
         """softmax(logits) for the metrics; column 1 for binary tasks (STiLModel.py:352-357, 450-457, 526-528)."""
-        p = ops.softmax_rows(logits.detach().contiguous())
-        return p[:, 1].contiguous() if self.hp.num_classes == 2 else p
+        return self._task_scores(ops.softmax_rows(logits.detach().contiguous()))
+
+    def _task_scores(self, probs):
+        return probs[:, 1].contiguous() if self.hp.num_classes == 2 else probs
 
     def freeze(self):
         """LightningModule.freeze(): no parameter requires grad, eval mode (trainers/evaluate.py:206, trainers/test.py:85)."""
@@ -633,281 +631,48 @@ class STiLModel(_Base):
 
     def test_step(self, batch, _=None):
         """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
-        With `tta` and tta_method "tent" / "eata" the batch first adapts the model (_tent_step / _eata_step) and the scores
+        With `tta` and tta_method "tent" / "eata" the batch first adapts the model (tta.tent_step / tta.eata_step) and the scores
         are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted."""
         if self._tta_on():
-            step = {"eata": self._eata_step, "bn_adapt": self._bn_adapt_step}.get(self.hp.tta_method, self._tent_step)
-            return step(batch)
+            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step}[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()
             dev = self.prototypes.device
             y_hat = self.model.forward((x[0].to(dev, torch.float32).contiguous(), x[1].to(dev, torch.float32).contiguous()), train=False)[0]
-            p = self._metric_probs(y_hat)
-            self.acc_test(p, y.to(dev))
-            self.auc_test(p, y.to(dev))
-            return p
+            return self._score_test(ops.softmax_rows(y_hat.detach().contiguous()), y)
 
-    # ------------------------------------------------------------------ test-time adaptation (TENT)
-    @staticmethod
-    def _check_tta(hp):
-        if hp.tta_method not in _TTA_METHODS:
-            raise ValueError(f"Unknown tta_method {hp.tta_method!r}: valid are {_TTA_METHODS}")
-        if hp.tta_params not in _TTA_PARAMS:
-            raise ValueError(f"Unknown tta_params {hp.tta_params!r}: valid are {_TTA_PARAMS}")
-        N = hp.tta_bn_prior
-        if N is not None and (isinstance(N, bool) or not isinstance(N, (int, float)) or not math.isfinite(N) or N < 0):
-            raise ValueError(f"tta_bn_prior must be None or a finite number >= 0, not {N!r}")
-        if hp.tta_method is not None and hp.tabular_encoder == "saint":
-            raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
+    def _score_test(self, probs, y):
+        """STiLModel.py:526-531: the scores of softmax rows `probs` (column 1 for binary tasks) into acc_test / auc_test; -> the scores."""
+        p = self._task_scores(probs)
+        y = y.to(probs.device)
+        self.acc_test(p, y)
+        self.auc_test(p, y)
+        return p
 
+    # ------------------------------------------------------------------ test-time adaptation: tta.py holds it, these delegate
     def _tta_on(self) -> bool:
-        return bool(getattr(self.hp, "tta", False)) and self.hp.tta_method in ("tent", "eata", "bn_adapt")
+        return tta.enabled(self.hp)
 
     def tta_param_names(self):
-        """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
-        BNs included); with tta_params == "norm" also of every LayerNorm of model.encoder_tabular and model.transformer."""
-        groups = [("model.encoder_imaging", self.model.encoder_imaging, nn.BatchNorm2d)]
-        if self.hp.tta_params == "norm":
-            groups += [("model.encoder_tabular", self.model.encoder_tabular, nn.LayerNorm), ("model.transformer", self.model.transformer, nn.LayerNorm)]
-        out = []
-        for prefix, root, kind in groups:
-            for n, mod in root.named_modules():
-                if isinstance(mod, kind):
-                    out += [f"{prefix}.{n}.weight", f"{prefix}.{n}.bias"]
-        return out
-
-    def _drop_tta(self):
-        """Forget the adaptation state (moments, step counts, source values; EATA's running mean of predictions and its Fisher
-        estimate, which belongs to the weights it was estimated on): load_state_dict calls this."""
-        self._tent = None
+        """The adapted set A, as state_dict names (tta.param_names)."""
+        return tta.param_names(self)
 
     def reset_tta(self):
-        """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset_tta),
-        moments and step counts cleared; the next adapted batch takes the source values afresh.  EATA: the running mean of
-        the selected predictions is cleared too, the Fisher estimate is kept."""
-        if self._tent is not None:
-            with torch.inference_mode(False):
-                self._tent.restore()
-                self._tent.clear_moments()
-                self._tent.source = None
-                if isinstance(self._tent, EataState):
-                    self._tent.clear_probs()
-
-    def _tent_state(self) -> TentState:
-        if self._tent is None:
-            names = [n[len("model."):] for n in self.tta_param_names()]   # FlatState names the backbone's own parameters
-            if self.hp.tta_method == "eata":
-                self._tent = EataState(self.flat, names, self.hp.num_classes)
-            else:
-                self._tent = TentState(self.flat, names)
-        return self._tent
-
-    def _tent_step(self, batch):
-        """TENT (Wang et al., ICLR 2021) on one test batch: forward with batch-statistics BatchNorm (running buffers untouched,
-        no MI-layer dropout), loss = mean row entropy of softmax(out_m), gradients for A only (no weight-gradient products),
-        one Adam step over A (tta_lr, betas (0.9, 0.999), eps 1e-8, no weight decay).  The scores are softmax(out_m) of this
-        forward, before the update.  Rank-local: no collectives.  Works after freeze() and inside torch.inference_mode()."""
-        x, y = batch
-        hp = self.hp
-        with torch.inference_mode(False):
-            self.setup_device()
-            dev = self.prototypes.device
-            x_img, x_tab = self._tta_inputs(x)
-            st = self._tent_state()
-            if hp.tta_episodic:
-                if st.source is not None:
-                    st.restore()
-                st.clear_moments()
-            if st.source is None:
-                st.snapshot()
-            with self._tta_scope(st):
-                self.flat.refresh_layouts(student=True, teacher=False)
-                with torch.enable_grad(), st.redirect():
-                    with self._tta_bn_scope(x_img.shape[0]):
-                        out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
-                    loss, probs = ops.entropy(out_m)
-                    loss.backward()
-                st.adam_step(hp.tta_lr)
-            self.last_tta = dict(loss=loss.detach(), y_hat_m=out_m.detach(), probs=probs)
-            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
-            y = y.to(dev)
-            self.acc_test(p, y)
-            self.auc_test(p, y)
-        return p
-
-    def _bn_adapt_step(self, batch):
-        """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the adapting forward of _tent_step (BatchNorm
-        statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
-        No adapted set, no gradient, no optimiser, no state: reset_tta() and tta_episodic have nothing to act on."""
-        x, y = batch
-        hp = self.hp
-        with torch.inference_mode(False), torch.no_grad():
-            self.setup_device()
-            dev = self.prototypes.device
-            x_img, x_tab = self._tta_inputs(x)
-            self.flat.refresh_layouts(student=True, teacher=False)
-            with self._tta_bn_scope(x_img.shape[0]):
-                out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
-            probs = ops.softmax_rows(out_m)
-            self.last_tta = dict(y_hat_m=out_m, probs=probs)
-            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
-            y = y.to(dev)
-            self.acc_test(p, y)
-            self.auc_test(p, y)
-        return p
-
-    # ------------------------------------------------------------------ shared by the TENT and EATA steps
-    @contextlib.contextmanager
-    def _tta_bn_scope(self, B):
-        """the BatchNorm of an adapting forward over B images: batch statistics, running buffers untouched; with tta_bn_prior = N
-        blended with the source statistics at rho = B / (N + B) (a short last batch gets its own rho)"""
-        with ops.frozen_bn_stats():
-            if self.hp.tta_bn_prior is None:
-                yield
-            else:
-                with ops.bn_prior(self.hp.tta_bn_prior, B):
-                    yield
-
-    @contextlib.contextmanager
-    def _tta_scope(self, st):
-        """requires_grad on A only, no gradient collectives (adaptation is per rank); flags and the exchange restored after"""
-        adapted = {id(t) for t in st.tensors}
-        flags = [(q, q.requires_grad) for q in self.parameters()]
-        exchange, ops._exchange = ops._exchange, None
-        try:
-            for q, _ in flags:
-                q.requires_grad_(id(q) in adapted)
-            yield
-        finally:
-            ops._exchange = exchange
-            for q, f in flags:
-                q.requires_grad_(f)
-
-    def _tta_inputs(self, x):
-        dev = self.prototypes.device
-        x_img, x_tab = (t.to(dev, torch.float32).contiguous() for t in x[:2])
-        if x_img.is_inference():
-            x_img = x_img.clone()
-        if x_tab.is_inference():
-            x_tab = x_tab.clone()
-        return x_img, x_tab
-
-    # ------------------------------------------------------------------ test-time adaptation (EATA)
-    def _eata_state(self) -> EataState:
-        if self.hp.tta_method != "eata":
-            raise ValueError(f"the Fisher estimate belongs to tta_method 'eata' (this model: {self.hp.tta_method!r})")
-        self.setup_device()
-        return self._tent_state()
-
-    def _eata_step(self, batch):
-        """EATA (Niu et al., ICML 2022) on one test batch: TENT's forward (batch-statistics BatchNorm, no MI-layer dropout) and
-        input-gradient-only backward, with (1) the loss restricted to the reliable (H_r < tta_e_margin) and non-redundant
-        (|cos(m, p_r)| < tta_d_margin, m = running mean of the selected predictions) rows, weighted by exp(E0 - H_r) and
-        averaged over the n selected rows, and (2) when a Fisher estimate is loaded, the anchor tta_fisher_alpha sum F (A - A0)^2
-        added to the loss and its gradient to A's.  One Adam step over A if and only if n > 0: n, the counts and that gate stay
-        on the device (stil_eata_rows writes the gated Adam mask), so the step reads nothing back.  The scores are softmax(out_m)
-        of this forward.  With tta_episodic, m is cleared and A restored before each batch: the redundancy filter and the
-        anchor are inert there (m is always invalid, A - A0 = 0)."""
-        x, y = batch
-        hp = self.hp
-        with torch.inference_mode(False):
-            self.setup_device()
-            dev = self.prototypes.device
-            x_img, x_tab = self._tta_inputs(x)
-            st = self._tent_state()
-            if hp.tta_episodic:
-                if st.source is not None:
-                    st.restore()
-                st.clear_moments()
-                st.clear_probs()
-            if st.source is None:
-                st.snapshot()
-            e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
-            with self._tta_scope(st):
-                self.flat.refresh_layouts(student=True, teacher=False)
-                with torch.enable_grad(), st.redirect():
-                    with self._tta_bn_scope(x_img.shape[0]):
-                        out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
-                    loss_ent, probs, info = ops.eata_entropy(out_m, e0, hp.tta_d_margin, hp.tta_probs_momentum, st.m, st.m_valid,
-                                                             st.active, st.gate)
-                    loss_ent.backward()
-                loss_anchor = torch.zeros((1,), dtype=torch.float32, device=dev)
-                if st.fisher is not None:
-                    st.anchor(hp.tta_fisher_alpha, loss_anchor)
-                st.gated_adam_step(hp.tta_lr)
-            loss_ent = loss_ent.detach()
-            self.last_tta = dict(loss=loss_ent + loss_anchor[0], y_hat_m=out_m.detach(), probs=probs, n_selected=info["counts"][0],
-                                 n_reliable=info["counts"][1], loss_entropy=loss_ent, loss_anchor=loss_anchor[0],
-                                 selected=info["sel"], reliable=info["rel"], entropy=info["H"], cos=info["cos"], weight=info["w"])
-            p = probs[:, 1].contiguous() if hp.num_classes == 2 else probs
-            y = y.to(dev)
-            self.acc_test(p, y)
-            self.auc_test(p, y)
-        return p
+        """A <- its source values, the adaptation state cleared, EATA's Fisher estimate kept (tta.reset)."""
+        tta.reset(self)
 
     def estimate_tta_fisher(self, batches, max_batches: Optional[int] = None):
-        """EATA's Fisher estimate of A at the CURRENT parameters (call it on the source model: before the first adapted batch
-        or after reset_tta()), from `batches` of source-like data laid out as test_step's (labels unused): per batch, the
-        forward of the adapting step, y_r = argmax_k out_m[r] (first maximum), l = mean_r CE(out_m[r], y_r), g = dl/dA;
-        F = (1/N) sum over the batches of g^2.  No parameter, BatchNorm buffer, teacher, prototype or training slab is written.
-        `batches` without a len() and no max_batches are materialised first (N scales every term)."""
-        with torch.inference_mode(False):
-            st = self._eata_state()
-            try:
-                N = len(batches)
-            except TypeError:
-                N = None
-            if max_batches is not None:
-                N = int(max_batches) if N is None else min(N, int(max_batches))
-            if N is None:
-                batches = list(batches)
-                N = len(batches)
-            if N < 1:
-                raise ValueError("estimate_tta_fisher needs at least one batch")
-            st.new_fisher()
-            dev = self.prototypes.device
-            seen = 0
-            with self._tta_scope(st):
-                for batch in batches:
-                    if seen >= N:
-                        break
-                    x_img, x_tab = self._tta_inputs(batch[0])
-                    self.flat.refresh_layouts(student=True, teacher=False)
-                    with torch.enable_grad(), st.redirect():
-                        with self._tta_bn_scope(x_img.shape[0]):
-                            out_m = self.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
-                        R, K = out_m.shape
-                        onehot = torch.empty((R, K), dtype=torch.float32, device=dev)
-                        mask = torch.empty((R,), dtype=torch.float32, device=dev)
-                        idx = torch.empty((R,), dtype=torch.int32, device=dev)
-                        lib().onehot_argmax(_p(out_m.detach()), R, K, 0.0, _p(onehot), _p(mask), _p(idx), _stream())
-                        ops.CEHardFn.apply(out_m, idx.long()).backward()
-                    st.fisher_accum(1.0 / N)
-                    seen += 1
-            if seen < N:  # an iterable shorter than max_batches: the mean is over the batches seen
-                if seen == 0:
-                    st.fisher = None
-                    raise ValueError("estimate_tta_fisher needs at least one batch")
-                st.fisher.mul_(N / seen)
-        return seen
+        """EATA's Fisher estimate of A at the current parameters from `batches`; -> the number of batches used (tta.estimate_fisher)."""
+        return tta.estimate_fisher(self, batches, max_batches)
 
     def tta_fisher_state(self) -> Dict[str, torch.Tensor]:
-        """{state_dict name of a member of A: its Fisher estimate} (copies; {} when none is loaded).  Not part of state_dict(),
-        whose keys are the reference's."""
-        st = self._tent
-        if not isinstance(st, EataState) or st.fisher is None:
-            return {}
-        return dict(zip(self.tta_param_names(), st.fisher_tensors()))
+        """{state_dict name of a member of A: its Fisher estimate}, {} when none is loaded (tta.fisher_state)."""
+        return tta.fisher_state(self)
 
     def load_tta_fisher(self, fisher: Dict[str, torch.Tensor]):
-        """Load a Fisher estimate saved by tta_fisher_state(); the keys must be exactly tta_param_names()."""
-        names = self.tta_param_names()
-        if set(fisher.keys()) != set(names):
-            raise ValueError(f"Fisher estimate for {len(fisher)} tensors, the adapted set has {len(names)}: "
-                             f"missing {sorted(set(names) - set(fisher))[:3]}, unexpected {sorted(set(fisher) - set(names))[:3]}")
-        with torch.inference_mode(False):
-            self._eata_state().load_fisher([fisher[n] for n in names])
+        """Load a Fisher estimate saved by tta_fisher_state() (tta.load_fisher)."""
+        tta.load_fisher(self, fisher)
 
     def test_epoch_end(self, _=None):
         """STiLModel.py:535-543."""

@@ -1,0 +1,487 @@
+"""Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
+al., ICML 2022) and the forward-only "bn_adapt" baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
+
+Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
+    tent_step              entropy           -> Adam over A
+    eata_step              eata_entropy      -> Fisher anchor (when an estimate is loaded) -> Adam over A gated by n > 0
+    estimate_fisher        argmax_ce         -> fisher += g^2 / N
+    bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState`) lives in `model._tent`.
+Adaptation is rank-local (no collectives) and composes no launch of the training step."""
+from __future__ import annotations
+
+import contextlib
+import math
+from typing import Dict, List, Optional
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import lib
+from .flat import ALIGN, FlatState, _round_up
+from .ops import _chk, _p, _scale_by, _stream, join_side
+
+METHODS = (None, "tent", "eata", "bn_adapt")
+PARAMS = ("bn", "norm")
+
+
+def check_hparams(hp):
+    if hp.tta_method not in METHODS:
+        raise ValueError(f"Unknown tta_method {hp.tta_method!r}: valid are {METHODS}")
+    if hp.tta_params not in PARAMS:
+        raise ValueError(f"Unknown tta_params {hp.tta_params!r}: valid are {PARAMS}")
+    N = hp.tta_bn_prior
+    if N is not None and (isinstance(N, bool) or not isinstance(N, (int, float)) or not math.isfinite(N) or N < 0):
+        raise ValueError(f"tta_bn_prior must be None or a finite number >= 0, not {N!r}")
+    if hp.tta_method is not None and hp.tabular_encoder == "saint":
+        raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
+
+
+def enabled(hp) -> bool:
+    return bool(getattr(hp, "tta", False)) and hp.tta_method in METHODS[1:]
+
+
+def param_names(model) -> List[str]:
+    """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
+    BNs included); with tta_params == "norm" also of every LayerNorm of model.encoder_tabular and model.transformer."""
+    groups = [("model.encoder_imaging", model.model.encoder_imaging, nn.BatchNorm2d)]
+    if model.hp.tta_params == "norm":
+        groups += [("model.encoder_tabular", model.model.encoder_tabular, nn.LayerNorm), ("model.transformer", model.model.transformer, nn.LayerNorm)]
+    out = []
+    for prefix, root, kind in groups:
+        for n, mod in root.named_modules():
+            if isinstance(mod, kind):
+                out += [f"{prefix}.{n}.weight", f"{prefix}.{n}.bias"]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- losses
+class EntropyFn(torch.autograd.Function):
+    """TENT's loss (Wang et al., ICLR 2021): mean over rows of H(softmax(z)), H(p) = -sum_k p_k log p_k, for test-time
+    adaptation in STiLModel.test_step (STiLModel.py:523-524).  -> (loss, probabilities); the probabilities (no gradient)
+    are the scores the step reports, so no separate softmax launch runs.  One launch forms lse, p, the row entropies and
+    dZ / rows (stil_entropy_rows); backward scales dZ by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, z):
+        _chk(z)
+        R, K = z.shape
+        dev = z.device
+        lse = torch.empty((R,), dtype=torch.float64, device=dev)
+        p = torch.empty_like(z)
+        h = torch.empty((R,), dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lib().entropy_rows(_p(z), K, R, K, 1.0 / R, _p(lse), _p(p), K, _p(h), _p(dz), K, _p(loss), _stream())
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return _scale_by(dz, g)
+
+
+def entropy(z):
+    """-> (mean row entropy of softmax(z) [autograd], softmax(z) [no grad], {})"""
+    return EntropyFn.apply(z.contiguous()) + ({},)
+
+
+class EataEntropyFn(torch.autograd.Function):
+    """EATA's loss (Niu et al., ICML 2022) beside EntropyFn: (1/n) sum over the selected rows of w_r H_r, the selection
+    (reliable: H_r < e_margin; non-redundant: |cos(m, p_r)| < d_margin), the weights w_r = exp(e_margin - H_r), the update of
+    the running mean m and the gate of the Adam step, all in stil_eata_rows: n stays on the device.
+    -> (loss, probabilities, info); info = dict(H, cos, w, rel, sel, counts [n, n_reliable, m valid before, -], lse).
+    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient; w carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, e_margin, d_margin, momentum, m, m_valid, active, gate, info):
+        _chk(z, m, m_valid, active, gate)
+        R, K = z.shape
+        dev = z.device
+        lse, hd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
+        p = torch.empty_like(z)
+        h, c, w = (torch.empty((R,), dtype=torch.float32, device=dev) for _ in range(3))
+        rel, sel = (torch.empty((R,), dtype=torch.uint8, device=dev) for _ in range(2))
+        dz = torch.empty_like(z)
+        counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nt = 0 if active is None else active.numel()
+        lib().eata_rows(_p(z), K, R, K, float(e_margin), float(d_margin), float(momentum), 1.0, _p(m), _p(m_valid), _p(lse), _p(hd), _p(p), K,
+                        _p(h), _p(c), _p(w), _p(rel), _p(sel), _p(dz), K, _p(counts), _p(loss), _p(active), _p(gate), nt, _stream())
+        info.update(H=h, cos=c, w=w, rel=rel, sel=sel, counts=counts, lse=lse)
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return (_scale_by(dz, g),) + (None,) * 8
+
+
+def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=None):
+    """-> (EATA's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates m / m_valid / gate."""
+    info = {}
+    loss, p = EataEntropyFn.apply(z.contiguous(), e_margin, d_margin, momentum, m, m_valid, active, gate, info)
+    return loss, p, info
+
+
+def argmax_ce(z):
+    """-> (mean_r CE(z[r], argmax_k z[r]) (first maximum) [autograd], None, {}): the loss of the Fisher estimate"""
+    R, K = z.shape
+    onehot = torch.empty((R, K), dtype=torch.float32, device=z.device)
+    mask = torch.empty((R,), dtype=torch.float32, device=z.device)
+    idx = torch.empty((R,), dtype=torch.int32, device=z.device)
+    lib().onehot_argmax(_p(z.detach()), R, K, 0.0, _p(onehot), _p(mask), _p(idx), _stream())
+    return ops.CEHardFn.apply(z, idx.long()), None, {}
+
+
+# ---------------------------------------------------------------------------------------------- state
+class TentState:
+    """Test-time adaptation state over the flat slab (TENT, Wang et al., ICLR 2021; STiLModel.test_step): the adapted set A
+    (`names`, a subset of FlatState.names), its own gradient slab and Adam moments / step counts in the student slab's
+    layout (stil_adam_step with `active` = A), and the source values of A.  The training slabs (FlatState._grads,
+    exp_avg, exp_avg_sq, steps) are never written: during a pass every parameter's gradient slot points into this
+    state's slab (`redirect`)."""
+
+    def __init__(self, flat: FlatState, names: List[str]):
+        self.flat = flat
+        ids = [flat.names.index(n) for n in names]
+        self.ids = ids
+        self.tensors = [flat.tensors[i] for i in ids]
+        dev = flat.params.device
+        self.grads = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(flat.total, dtype=torch.float32, device=dev)
+        self.steps = torch.zeros(len(flat.tensors), dtype=torch.int32, device=dev)
+        act = torch.zeros(len(flat.tensors), dtype=torch.uint8)
+        act[ids] = 1
+        self.active = act.to(dev)
+        base = flat._grads.data_ptr()
+        self._slots = [self.grads[(t._gslot.data_ptr() - base) // 4:][:t.numel()].view(t.shape) for t in flat.tensors]
+        self.source: Optional[List[torch.Tensor]] = None
+
+    @torch.no_grad()
+    def snapshot(self):
+        self.source = [t.detach().clone() for t in self.tensors]
+
+    @torch.no_grad()
+    def reset(self):
+        """A <- its source values (as it is before the first snapshot), and what a new episode clears: moments, step counts."""
+        if self.source is not None:
+            torch._foreach_copy_([t.data for t in self.tensors], self.source)
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.steps.zero_()
+
+    @contextlib.contextmanager
+    def redirect(self):
+        """Gradient slots -> this state's (zeroed) slab for the duration; slots, `_stil_touched` flags restored after."""
+        ts = self.flat.tensors
+        saved = [(t._gslot, t._stil_touched) for t in ts]
+        self.grads.zero_()
+        for t, s in zip(ts, self._slots):
+            t._gslot, t._stil_touched = s, False
+        try:
+            yield
+        finally:
+            join_side()
+            for t, (g, touched) in zip(ts, saved):
+                t._gslot, t._stil_touched = g, touched
+
+    @torch.no_grad()
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, mask=None):
+        """Adam over A, no weight decay.  mask: the per-tensor mask to step under instead of `active` (EATA's `gate`: with
+        n == 0 neither A, nor its moments, nor its step counts move)."""
+        f = self.flat
+        lib().adam_step(_p(f.params), _p(self.grads), _p(self.exp_avg), _p(self.exp_avg_sq), _p(f.chunk2tensor), _p(self.steps),
+                        _p(self.active if mask is None else mask), len(f.tensors), f.total, float(lr), float(betas[0]), float(betas[1]),
+                        float(eps), 0.0, 1.0, _stream())
+
+
+class EataState(TentState):
+    """TentState plus what EATA adds (Niu et al., ICML 2022): the running mean `m` [K] of the selected predictions and its
+    validity flag, the gated copy of the Adam mask (`gate` = active and n > 0, written by stil_eata_rows), and the Fisher
+    estimate.  Fisher and source values are COMPACT: `achunks` lists the 1024-float slab chunks of A, chunk j of `fisher` /
+    `theta0` belongs to slab chunk achunks[j] (`source` holds views into `theta0`, so reset() restores as TentState's).  For A =
+    the 106 BatchNorm affines of a ResNet-50 that is 114 chunks: 456 KiB each, against 178 MiB for a slab in the flat layout."""
+
+    def __init__(self, flat: FlatState, names: List[str], num_classes: int):
+        super().__init__(flat, names)
+        dev = flat.params.device
+        base = flat.params.data_ptr()
+        chunks, self._spans = [], []
+        for t in self.tensors:
+            o = (t.data_ptr() - base) // 4
+            self._spans.append((len(chunks) * ALIGN, t.numel()))
+            chunks += list(range(o // ALIGN, (o + _round_up(t.numel())) // ALIGN))
+        self.n_achunks = len(chunks)
+        self.achunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
+        self.theta0 = torch.zeros(self.n_achunks * ALIGN, dtype=torch.float32, device=dev)
+        self.fisher: Optional[torch.Tensor] = None
+        self.partial = torch.zeros(max(self.n_achunks, 1), dtype=torch.float64, device=dev)
+        self.m = torch.zeros(num_classes, dtype=torch.float32, device=dev)
+        self.m_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gate = torch.zeros_like(self.active)
+
+    def _compact_views(self, buf):
+        return [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._spans, self.tensors)]
+
+    @torch.no_grad()
+    def snapshot(self):
+        self.source = self._compact_views(self.theta0)
+        torch._foreach_copy_(self.source, [t.detach() for t in self.tensors])
+
+    @torch.no_grad()
+    def reset(self):
+        """TentState.reset, and the running mean of the selected predictions is cleared too; the Fisher estimate is kept."""
+        super().reset()
+        self.m.zero_()
+        self.m_valid.zero_()
+
+    # ---- Fisher estimate: one tensor per member of A <-> the compact slab
+    @torch.no_grad()
+    def new_fisher(self):
+        self.fisher = torch.zeros_like(self.theta0)
+
+    @torch.no_grad()
+    def fisher_accum(self, scale: float):
+        """fisher += grads^2 * scale over A's chunks of this state's gradient slab"""
+        f = self.flat
+        lib().eata_fisher_accum(_p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks, _p(f.chunk2tensor),
+                                _p(self.active), len(f.tensors), f.total, float(scale), _stream())
+
+    @torch.no_grad()
+    def anchor(self, alpha: float, out: torch.Tensor):
+        """grads += 2 alpha F (theta - theta0) over A's chunks; out[0] = alpha sum F (theta - theta0)^2"""
+        f = self.flat
+        lib().eata_anchor(_p(f.params), _p(self.theta0), _p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks,
+                          _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total, float(alpha), _p(self.partial), _p(out),
+                          _stream())
+
+    def fisher_tensors(self) -> List[torch.Tensor]:
+        return [v.clone() for v in self._compact_views(self.fisher)]
+
+    @torch.no_grad()
+    def load_fisher(self, tensors: List[torch.Tensor]):
+        self.new_fisher()
+        views = self._compact_views(self.fisher)
+        for v, t in zip(views, tensors):
+            if tuple(v.shape) != tuple(t.shape):
+                raise ValueError(f"Fisher estimate of shape {tuple(t.shape)} for a parameter of shape {tuple(v.shape)}")
+        torch._foreach_copy_(views, [t.detach().to(self.fisher.device, torch.float32) for t in tensors])
+
+
+def _state(model) -> TentState:
+    """model._tent, created on first use (the model is on its device)"""
+    if model._tent is None:
+        names = [n[len("model."):] for n in param_names(model)]   # FlatState names the backbone's own parameters
+        if model.hp.tta_method == "eata":
+            model._tent = EataState(model.flat, names, model.hp.num_classes)
+        else:
+            model._tent = TentState(model.flat, names)
+    return model._tent
+
+
+def _eata_state(model) -> EataState:
+    if model.hp.tta_method != "eata":
+        raise ValueError(f"the Fisher estimate belongs to tta_method 'eata' (this model: {model.hp.tta_method!r})")
+    model.setup_device()
+    return _state(model)
+
+
+def _begin(model) -> TentState:
+    """The state a batch adapts under: with tta_episodic A is restored and the state reset before every batch; the source
+    values are taken whenever none are held (the first adapted batch since construction / load_state_dict / reset)."""
+    model.setup_device()
+    st = _state(model)
+    if model.hp.tta_episodic:
+        st.reset()
+    if st.source is None:
+        st.snapshot()
+    return st
+
+
+def drop(model):
+    """Forget the adaptation state (moments, step counts, source values; EATA's running mean of predictions and its Fisher
+    estimate, which belongs to the weights it was estimated on): load_state_dict calls this."""
+    model._tent = None
+
+
+def reset(model):
+    """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset),
+    moments and step counts cleared; the next adapted batch takes the source values afresh.  EATA: the running mean of
+    the selected predictions is cleared too, the Fisher estimate is kept."""
+    if model._tent is not None:
+        with torch.inference_mode(False):
+            model._tent.reset()
+            model._tent.source = None
+
+
+# ---------------------------------------------------------------------------------------------- the adapting pass
+def _inputs(model, x):
+    dev = model.prototypes.device
+    x_img, x_tab = (t.to(dev, torch.float32).contiguous() for t in x[:2])
+    if x_img.is_inference():
+        x_img = x_img.clone()
+    if x_tab.is_inference():
+        x_tab = x_tab.clone()
+    return x_img, x_tab
+
+
+def _forward(model, x_img, x_tab):
+    """The adapting forward -> out_m: no MI-layer dropout; BatchNorm over the B images of this batch by batch statistics,
+    running buffers untouched; with tta_bn_prior = N blended with the source statistics at rho = B / (N + B) (a short last
+    batch gets its own rho)."""
+    N = model.hp.tta_bn_prior
+    with ops.frozen_bn_stats(), (contextlib.nullcontext() if N is None else ops.bn_prior(N, x_img.shape[0])):
+        return model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+
+
+@contextlib.contextmanager
+def _grads_of(model, st):
+    """requires_grad on A only, no gradient collectives (adaptation is per rank), layouts of the current weights, grad mode on
+    and every gradient slot in st's slab; flags, exchange and slots restored after"""
+    adapted = {id(t) for t in st.tensors}
+    flags = [(q, q.requires_grad) for q in model.parameters()]
+    exchange, ops._exchange = ops._exchange, None
+    try:
+        for q, _ in flags:
+            q.requires_grad_(id(q) in adapted)
+        model.flat.refresh_layouts(student=True, teacher=False)
+        with torch.enable_grad(), st.redirect():
+            yield
+    finally:
+        ops._exchange = exchange
+        for q, f in flags:
+            q.requires_grad_(f)
+
+
+def adapting_pass(model, x, st, loss_fn):
+    """One adapting forward and backward on the inputs x = (images, table, ...) of a batch: the forward of `_forward`,
+    loss_fn(out_m) -> (loss, probs, extras), gradients of the loss for A only (no weight-gradient products) in st.grads.
+    Writes st.grads and whatever loss_fn writes; never a parameter, BatchNorm buffer, teacher, prototype or training slab.
+    The caller holds torch.inference_mode(False).  -> (out_m, loss, probs, extras), detached."""
+    x_img, x_tab = _inputs(model, x)
+    with _grads_of(model, st):
+        out_m = _forward(model, x_img, x_tab)
+        loss, probs, extras = loss_fn(out_m)
+        loss.backward()
+    return out_m.detach(), loss.detach(), probs, extras
+
+
+def tent_step(model, batch):
+    """TENT (Wang et al., ICLR 2021) on one test batch: forward with batch-statistics BatchNorm (running buffers untouched,
+    no MI-layer dropout), loss = mean row entropy of softmax(out_m), gradients for A only (no weight-gradient products),
+    one Adam step over A (tta_lr, betas (0.9, 0.999), eps 1e-8, no weight decay).  Writes A, its own moments and step counts,
+    acc_test / auc_test and last_tta; never the training slabs, buffers, teacher or prototypes.  The scores are softmax(out_m)
+    of this forward, before the update.  Rank-local: no collectives.  Works after freeze() and inside torch.inference_mode()."""
+    x, y = batch
+    with torch.inference_mode(False):
+        st = _begin(model)
+        out_m, loss, probs, _ = adapting_pass(model, x, st, entropy)
+        st.adam_step(model.hp.tta_lr)
+        model.last_tta = dict(loss=loss, y_hat_m=out_m, probs=probs)
+        return model._score_test(probs, y)
+
+
+def eata_step(model, batch):
+    """EATA (Niu et al., ICML 2022) on one test batch: TENT's forward (batch-statistics BatchNorm, no MI-layer dropout) and
+    input-gradient-only backward, with (1) the loss restricted to the reliable (H_r < tta_e_margin) and non-redundant
+    (|cos(m, p_r)| < tta_d_margin, m = running mean of the selected predictions) rows, weighted by exp(E0 - H_r) and
+    averaged over the n selected rows, and (2) when a Fisher estimate is loaded, the anchor tta_fisher_alpha sum F (A - A0)^2
+    added to the loss and its gradient to A's.  One Adam step over A if and only if n > 0: n, the counts and that gate stay
+    on the device (stil_eata_rows writes the gated Adam mask), so the step reads nothing back.  Writes what tent_step writes
+    and m / m_valid; never the Fisher estimate.  The scores are softmax(out_m) of this forward.  With tta_episodic, m is
+    cleared and A restored before each batch: the redundancy filter and the anchor are inert there (m is always invalid,
+    A - A0 = 0)."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+        out_m, loss_ent, probs, info = adapting_pass(model, x, st, lambda z: eata_entropy(
+            z, e0, hp.tta_d_margin, hp.tta_probs_momentum, st.m, st.m_valid, st.active, st.gate))
+        loss_anchor = torch.zeros((1,), dtype=torch.float32, device=out_m.device)
+        if st.fisher is not None:
+            st.anchor(hp.tta_fisher_alpha, loss_anchor)
+        st.adam_step(hp.tta_lr, mask=st.gate)
+        model.last_tta = dict(loss=loss_ent + loss_anchor[0], y_hat_m=out_m, probs=probs, n_selected=info["counts"][0],
+                              n_reliable=info["counts"][1], loss_entropy=loss_ent, loss_anchor=loss_anchor[0],
+                              selected=info["sel"], reliable=info["rel"], entropy=info["H"], cos=info["cos"], weight=info["w"])
+        return model._score_test(probs, y)
+
+
+def bn_adapt_step(model, batch):
+    """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
+    statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
+    No adapted set, no gradient, no optimiser, no state: reset_tta() and tta_episodic have nothing to act on.  Writes
+    acc_test / auc_test and last_tta, nothing else; Adam never runs."""
+    x, y = batch
+    with torch.inference_mode(False), torch.no_grad():
+        model.setup_device()
+        x_img, x_tab = _inputs(model, x)
+        model.flat.refresh_layouts(student=True, teacher=False)
+        out_m = _forward(model, x_img, x_tab)
+        probs = ops.softmax_rows(out_m)
+        model.last_tta = dict(y_hat_m=out_m, probs=probs)
+        return model._score_test(probs, y)
+
+
+# ---------------------------------------------------------------------------------------------- EATA's Fisher estimate
+def estimate_fisher(model, batches, max_batches: Optional[int] = None) -> int:
+    """EATA's Fisher estimate of A at the CURRENT parameters (call it on the source model: before the first adapted batch
+    or after reset_tta()), from `batches` of source-like data laid out as test_step's (labels unused): per batch, the
+    adapting pass with y_r = argmax_k out_m[r] (first maximum), l = mean_r CE(out_m[r], y_r), g = dl/dA;
+    F = (1/N) sum over the batches of g^2.  No parameter, BatchNorm buffer, teacher, prototype or training slab is written,
+    and Adam never runs.  `batches` without a len() and no max_batches are materialised first (N scales every term).
+    -> the number of batches used."""
+    with torch.inference_mode(False):
+        st = _eata_state(model)
+        try:
+            N = len(batches)
+        except TypeError:
+            N = None
+        if max_batches is not None:
+            N = int(max_batches) if N is None else min(N, int(max_batches))
+        if N is None:
+            batches = list(batches)
+            N = len(batches)
+        if N < 1:
+            raise ValueError("estimate_tta_fisher needs at least one batch")
+        st.new_fisher()
+        seen = 0
+        for batch in batches:
+            if seen >= N:
+                break
+            adapting_pass(model, batch[0], st, argmax_ce)
+            st.fisher_accum(1.0 / N)
+            seen += 1
+        if seen < N:  # an iterable shorter than max_batches: the mean is over the batches seen
+            if seen == 0:
+                st.fisher = None
+                raise ValueError("estimate_tta_fisher needs at least one batch")
+            st.fisher.mul_(N / seen)
+    return seen
+
+
+def fisher_state(model) -> Dict[str, torch.Tensor]:
+    """{state_dict name of a member of A: its Fisher estimate} (copies; {} when none is loaded).  Not part of state_dict(),
+    whose keys are the reference's."""
+    st = model._tent
+    if getattr(st, "fisher", None) is None:
+        return {}
+    return dict(zip(param_names(model), st.fisher_tensors()))
+
+
+def load_fisher(model, fisher: Dict[str, torch.Tensor]):
+    """Load a Fisher estimate saved by fisher_state(); the keys must be exactly param_names()."""
+    names = param_names(model)
+    if set(fisher.keys()) != set(names):
+        raise ValueError(f"Fisher estimate for {len(fisher)} tensors, the adapted set has {len(names)}: "
+                         f"missing {sorted(set(names) - set(fisher))[:3]}, unexpected {sorted(set(fisher) - set(names))[:3]}")
+    with torch.inference_mode(False):
+        _eata_state(model).load_fisher([fisher[n] for n in names])

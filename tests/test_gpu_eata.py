@@ -648,6 +648,44 @@ def test_state_rules_reset_episodic_and_load_state_dict():
         mk_tent().load_tta_fisher(F)
 
 
+def test_fisher_estimate_from_iterables_without_len_short_and_empty():
+    """estimate_tta_fisher on a generator (materialised: the list's estimate bit for bit), on an iterable shorter than
+    max_batches (the N / seen rescale) and on empty ones.  The short path against the list, elementwise:
+    |a - b| <= 8 2^-24 max(|a|, |b|) + 2^-126, exact zeros equal.  Every term g^2 / N is non-negative, so relative errors add:
+    the list path rounds twice (one per accumulation), the short path three times (two accumulations, the rescale) and carries
+    the float32 1/5 scale; together at most 6 2^-24 to first order.  The floor covers subnormal g^2."""
+    hp, sd, mk = _small()
+    b1, b2 = T.to_dev(T.tta_batch(hp, 16, 11)), T.to_dev(T.tta_batch(hp, 16, 12))
+    ref = mk()
+    assert ref.estimate_tta_fisher([b1, b2]) == 2
+    F = ref.tta_fisher_state()
+    assert any(float(v.abs().max()) > 0 for v in F.values())
+    g = mk()
+    assert g.estimate_tta_fisher(b for b in (b1, b2)) == 2
+    Fg = g.tta_fisher_state()
+    assert set(Fg) == set(F)
+    for k in F:
+        assert torch.equal(Fg[k], F[k]), k
+    s = mk()
+    assert s.estimate_tta_fisher((b for b in (b1, b2)), max_batches=5) == 2
+    Fs = s.tta_fisher_state()
+    assert set(Fs) == set(F)
+    worst = 0.0
+    for k in F:
+        a, b = Fs[k].double(), F[k].double()
+        assert torch.equal(a == 0, b == 0), k
+        bound = 8 * 2.0 ** -24 * torch.maximum(a.abs(), b.abs()) + 2.0 ** -126
+        worst = max(worst, float(((a - b).abs() / bound).max()))
+        assert bool(((a - b).abs() <= bound).all()), (k, float(((a - b).abs() / bound).max()))
+    print(f"short iterable against the list: worst |a - b| / bound {worst:.3f}")
+    e = mk()
+    with pytest.raises(ValueError):
+        e.estimate_tta_fisher([])
+    with pytest.raises(ValueError):
+        e.estimate_tta_fisher(iter([]), 3)
+    assert e.tta_fisher_state() == {}
+
+
 def test_freeze_and_inference_mode():
     hp, sd, mk = _small()
     b, fb = T.to_dev(T.tta_batch(hp, 16, 14)), [T.to_dev(T.tta_batch(hp, 16, 15))]
