@@ -31,3 +31,4 @@ extern "C" int stil_device_count(void) {
 #include "state.hip"
 #include "tta.hip"
 #include "eata.hip"
+#include "infomax.hip"

@@ -46,7 +46,7 @@ _DEFAULTS = dict(
     tabular_encoder="transformer",  # "saint": the STiLModel_SAINT.py variant (also selected by algorithm_name == "STiL_SAINT")
     # test-time adaptation in test_step (the TODO of STiLModel.py:523-524): runs only when `tta` is truthy AND tta_method is set
     tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
-                         # | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
+                         # | "shot_im" (Liang et al., ICML 2020: entropy plus a batch-diversity term) | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
@@ -57,6 +57,9 @@ _DEFAULTS = dict(
     tta_d_margin=0.05,        # d: rows with |cos(running mean of selected predictions, p)| below it are non-redundant
     tta_probs_momentum=0.9,   # momentum of that running mean
     tta_fisher_alpha=2000.0,  # weight of the Fisher anchor (the paper's ImageNet value; its CIFAR runs use 1); inert without a Fisher estimate
+    # "shot_im" only: the batch-diversity term of SHOT's information maximisation (Liang et al., ICML 2020)
+    tta_div_weight=1.0,       # weight of sum_k pbar_k log(pbar_k + eps), pbar = the batch-mean prediction; 0 is "tent"; lower it under strong label shift
+    tta_div_eps=1e-5,         # eps inside that logarithm (SHOT's value)
 )
 
 
@@ -631,10 +634,11 @@ class STiLModel(_Base):
 
     def test_step(self, batch, _=None):
         """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
-        With `tta` and tta_method "tent" / "eata" the batch first adapts the model (tta.tent_step / tta.eata_step) and the scores
+        With `tta` and tta_method "tent" / "eata" / "shot_im" the batch first adapts the model (tta.tent_step / tta.eata_step /
+        tta.shot_im_step) and the scores
         are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted."""
         if self._tta_on():
-            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step}[self.hp.tta_method](self, batch)
+            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step}[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()

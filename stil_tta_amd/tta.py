@@ -1,9 +1,11 @@
 """Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
-al., ICML 2022) and the forward-only "bn_adapt" baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
+al., ICML 2022), SHOT-IM (Liang et al., ICML 2020) and the forward-only "bn_adapt" baseline, optionally under a source-statistics
+BatchNorm prior (tta_bn_prior).
 
 Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
     tent_step              entropy           -> Adam over A
     eata_step              eata_entropy      -> Fisher anchor (when an estimate is loaded) -> Adam over A gated by n > 0
+    shot_im_step           infomax           -> Adam over A
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
 A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState`) lives in `model._tent`.
@@ -22,7 +24,7 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-METHODS = (None, "tent", "eata", "bn_adapt")
+METHODS = (None, "tent", "eata", "bn_adapt", "shot_im")
 PARAMS = ("bn", "norm")
 
 
@@ -34,6 +36,11 @@ def check_hparams(hp):
     N = hp.tta_bn_prior
     if N is not None and (isinstance(N, bool) or not isinstance(N, (int, float)) or not math.isfinite(N) or N < 0):
         raise ValueError(f"tta_bn_prior must be None or a finite number >= 0, not {N!r}")
+    w, e = hp.tta_div_weight, hp.tta_div_eps
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+        raise ValueError(f"tta_div_weight must be a finite number >= 0, not {w!r}")
+    if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or e <= 0:
+        raise ValueError(f"tta_div_eps must be a finite number > 0, not {e!r}")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -126,6 +133,46 @@ def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=
     """-> (EATA's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates m / m_valid / gate."""
     info = {}
     loss, p = EataEntropyFn.apply(z.contiguous(), e_margin, d_margin, momentum, m, m_valid, active, gate, info)
+    return loss, p, info
+
+
+class InfoMaxFn(torch.autograd.Function):
+    """SHOT's information-maximisation loss (Liang et al., ICML 2020) beside EntropyFn: mean row entropy of softmax(z) plus
+    div_weight x D, D = sum_k pbar_k log(pbar_k + eps) with pbar the batch mean of the rows' softmax (minus the entropy of the
+    marginal: it penalises the batch that predicts one class everywhere).  stil_infomax_rows forms lse, p, the row entropies,
+    pbar, D and dZ / rows; the gradient couples the rows through pbar.  -> (loss, probabilities); info = dict(loss_entropy,
+    loss_diversity, marginal [K], H, lse), all on the device.  Backward scales dZ by the incoming gradient.  With
+    div_weight == 0 loss, probabilities and dZ are EntropyFn's bit for bit."""
+
+    @staticmethod
+    def forward(ctx, z, div_weight, eps, info):
+        _chk(z)
+        R, K = z.shape
+        dev = z.device
+        lse = torch.empty((R,), dtype=torch.float64, device=dev)
+        p = torch.empty_like(z)
+        h = torch.empty((R,), dtype=torch.float32, device=dev)
+        pbar = torch.empty((K,), dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z)
+        out = torch.empty((3,), dtype=torch.float32, device=dev)
+        ws = torch.empty((2 * K + R,), dtype=torch.float64, device=dev)
+        lib().infomax_rows(_p(z), K, R, K, 1.0 / R, float(div_weight), float(eps), _p(lse), _p(p), K, _p(h), _p(pbar), _p(dz), K,
+                           _p(out), _p(ws), _stream())
+        info.update(loss_entropy=out[1], loss_diversity=out[2], marginal=pbar, H=h, lse=lse)
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return out[0], p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return _scale_by(dz, g), None, None, None
+
+
+def infomax(z, div_weight=1.0, eps=1e-5):
+    """-> (mean row entropy + div_weight x D of softmax(z) [autograd], softmax(z) [no grad], info)"""
+    info = {}
+    loss, p = InfoMaxFn.apply(z.contiguous(), div_weight, eps, info)
     return loss, p, info
 
 
@@ -412,6 +459,24 @@ def eata_step(model, batch):
         model.last_tta = dict(loss=loss_ent + loss_anchor[0], y_hat_m=out_m, probs=probs, n_selected=info["counts"][0],
                               n_reliable=info["counts"][1], loss_entropy=loss_ent, loss_anchor=loss_anchor[0],
                               selected=info["sel"], reliable=info["rel"], entropy=info["H"], cos=info["cos"], weight=info["w"])
+        return model._score_test(probs, y)
+
+
+def shot_im_step(model, batch):
+    """SHOT-IM (Liang et al., ICML 2020; the baseline the TENT paper reports beside itself) on one test batch: tent_step with
+    the information-maximisation loss, mean row entropy + tta_div_weight x sum_k pbar_k log(pbar_k + tta_div_eps), pbar the mean
+    prediction of THIS batch (no running marginal).  SHOT's frozen classifier head holds by construction (A never contains
+    it); its pseudo-label term is not part of this method.  State, Adam, episodic mode, tta_bn_prior and what is written are
+    tent_step's; tta_div_weight = 0 is tent_step bit for bit.  last_tta: loss, loss_entropy, loss_diversity, marginal (pbar,
+    [K]), y_hat_m, probs, all on the device: the step reads nothing back."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        out_m, loss, probs, info = adapting_pass(model, x, st, lambda z: infomax(z, hp.tta_div_weight, hp.tta_div_eps))
+        st.adam_step(hp.tta_lr)
+        model.last_tta = dict(loss=loss, loss_entropy=info["loss_entropy"], loss_diversity=info["loss_diversity"],
+                              marginal=info["marginal"], y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
 
 
