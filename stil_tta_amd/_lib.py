@@ -1,5 +1,5 @@
 """ctypes binding of libstil_hip.so, generated from include/stil_hip.h, include/stil_tta.h, include/stil_eata.h,
-include/stil_bnprior.h and include/stil_infomax.h at import time.
+include/stil_bnprior.h, include/stil_infomax.h and include/stil_margent.h at import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -18,6 +18,7 @@ TTA_HEADER = os.path.join(_ROOT, "include", "stil_tta.h")   # test-time adaptati
 EATA_HEADER = os.path.join(_ROOT, "include", "stil_eata.h")  # EATA on top of TENT (a ledger of its own)
 BNPRIOR_HEADER = os.path.join(_ROOT, "include", "stil_bnprior.h")  # test-time BatchNorm with a source prior (a ledger of its own)
 INFOMAX_HEADER = os.path.join(_ROOT, "include", "stil_infomax.h")  # SHOT's information-maximisation loss (a ledger of its own)
+MARGENT_HEADER = os.path.join(_ROOT, "include", "stil_margent.h")  # MEMO's marginal entropy over augmented views (a ledger of its own)
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -94,6 +95,7 @@ class _Lib:
         self.protos.update(parse_header(EATA_HEADER))
         self.protos.update(parse_header(BNPRIOR_HEADER))
         self.protos.update(parse_header(INFOMAX_HEADER))
+        self.protos.update(parse_header(MARGENT_HEADER))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks
             fn.restype = restype

@@ -32,3 +32,4 @@ extern "C" int stil_device_count(void) {
 #include "tta.hip"
 #include "eata.hip"
 #include "infomax.hip"
+#include "margent.hip"

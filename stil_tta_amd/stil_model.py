@@ -47,6 +47,7 @@ _DEFAULTS = dict(
     # test-time adaptation in test_step (the TODO of STiLModel.py:523-524): runs only when `tta` is truthy AND tta_method is set
     tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
                          # | "shot_im" (Liang et al., ICML 2020: entropy plus a batch-diversity term) | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
+                         # | "marginal_entropy" (MEMO, Zhang et al., NeurIPS 2022: adapts on augmented views of each sample, scores the clean batch after the update)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
@@ -60,6 +61,10 @@ _DEFAULTS = dict(
     # "shot_im" only: the batch-diversity term of SHOT's information maximisation (Liang et al., ICML 2020)
     tta_div_weight=1.0,       # weight of sum_k pbar_k log(pbar_k + eps), pbar = the batch-mean prediction; 0 is "tent"; lower it under strong label shift
     tta_div_eps=1e-5,         # eps inside that logarithm (SHOT's value)
+    # "marginal_entropy" only: MEMO (Zhang, Levine, Finn, NeurIPS 2022), the entropy of the mean prediction over augmented views of each test sample
+    tta_views=32,                  # V: views per sample (the adapting pass runs on B x V rows)
+    tta_view_policy="hard_eval",   # the transform family of the views: contrastive | hard_eval | soft_eval | weak | strong (augment._policy)
+    tta_view_seed=2022,            # seed of the views' generator, which lives in the adaptation state
 )
 
 
@@ -636,9 +641,12 @@ class STiLModel(_Base):
         """STiLModel.py:517-533: softmax(y_hat) (column 1 for binary tasks) into acc_test / auc_test; returns the scores.
         With `tta` and tta_method "tent" / "eata" / "shot_im" the batch first adapts the model (tta.tent_step / tta.eata_step /
         tta.shot_im_step) and the scores
-        are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted."""
+        are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted.
+        With "marginal_entropy" (tta.marginal_entropy_step, MEMO) the model adapts on tta_views augmented views of every sample
+        and the scores are those of a forward of the clean batch AFTER the update: the one method that scores after it."""
         if self._tta_on():
-            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step}[self.hp.tta_method](self, batch)
+            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step,
+                    "marginal_entropy": tta.marginal_entropy_step}[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()

@@ -1,14 +1,17 @@
 """Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
-al., ICML 2022), SHOT-IM (Liang et al., ICML 2020) and the forward-only "bn_adapt" baseline, optionally under a source-statistics
-BatchNorm prior (tta_bn_prior).
+al., ICML 2022), SHOT-IM (Liang et al., ICML 2020), MEMO's marginal entropy over augmented views (Zhang et al., NeurIPS 2022) and
+the forward-only "bn_adapt" baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
 
 Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
     tent_step              entropy           -> Adam over A
     eata_step              eata_entropy      -> Fisher anchor (when an estimate is loaded) -> Adam over A gated by n > 0
     shot_im_step           infomax           -> Adam over A
+    marginal_entropy_step  marginal_entropy on V views of every sample (make_views) -> Adam over A -> the forward of
+                           bn_adapt_step on the clean batch: the one method whose scores come after the update
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState`) lives in `model._tent`.
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState`) lives in `model._tent`, and with
+it the augmenter of marginal_entropy_step's views (`TentState.views`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
 from __future__ import annotations
 
@@ -24,8 +27,9 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-METHODS = (None, "tent", "eata", "bn_adapt", "shot_im")
+METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy")
 PARAMS = ("bn", "norm")
+VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
 
 
 def check_hparams(hp):
@@ -41,6 +45,13 @@ def check_hparams(hp):
         raise ValueError(f"tta_div_weight must be a finite number >= 0, not {w!r}")
     if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or e <= 0:
         raise ValueError(f"tta_div_eps must be a finite number > 0, not {e!r}")
+    V, seed = hp.tta_views, hp.tta_view_seed
+    if isinstance(V, bool) or not isinstance(V, int) or V < 1:
+        raise ValueError(f"tta_views must be an int >= 1, not {V!r}")
+    if not isinstance(hp.tta_view_policy, str) or hp.tta_view_policy not in VIEW_POLICIES:
+        raise ValueError(f"Unknown tta_view_policy {hp.tta_view_policy!r}: valid are {VIEW_POLICIES}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:   # the generator takes no negative seed
+        raise ValueError(f"tta_view_seed must be an int >= 0, not {seed!r}")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -176,6 +187,48 @@ def infomax(z, div_weight=1.0, eps=1e-5):
     return loss, p, info
 
 
+class MarginalEntropyFn(torch.autograd.Function):
+    """MEMO's loss (Zhang, Levine, Finn, NeurIPS 2022) beside EntropyFn: z holds `views` consecutive rows per sample (row g V + v is
+    view v of sample g); the loss is the mean over the samples of the entropy of the sample's mean prediction over its views.
+    stil_marginal_entropy_groups forms lse, the marginals (through a log-sum-exp over the views, never the logarithm of an
+    underflowed mean), their entropies and dZ / groups.  -> loss; info = dict(marginal [G, K], marginal_entropy [G], lse, and
+    probs [G V, K] when asked for), all on the device.  Backward scales dZ by the incoming gradient.  With views == 1 it is
+    EntropyFn's loss."""
+
+    @staticmethod
+    def forward(ctx, z, groups, views, want_probs, info):
+        _chk(z)
+        R, K = z.shape
+        if R != groups * views:
+            raise ValueError(f"marginal_entropy: {R} rows are not {groups} samples x {views} views")
+        dev = z.device
+        lse = torch.empty((R,), dtype=torch.float64, device=dev)
+        p = torch.empty_like(z) if want_probs else None
+        pbar = torch.empty((groups, K), dtype=torch.float32, device=dev)
+        hbar = torch.empty((groups,), dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z)
+        out = torch.empty((1,), dtype=torch.float32, device=dev)
+        ws = torch.empty((groups * (K + (K + 255) // 256),), dtype=torch.float64, device=dev)
+        lib().marginal_entropy_groups(_p(z), K, groups, views, K, 1.0 / groups, _p(lse), _p(p), K, _p(pbar), K, _p(hbar), _p(dz), K,
+                                      _p(out), _p(ws), _stream())
+        info.update(marginal=pbar, marginal_entropy=hbar, lse=lse, probs=p)
+        ctx.save_for_backward(dz)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return _scale_by(dz, g), None, None, None, None
+
+
+def marginal_entropy(z, groups, views, want_probs=False):
+    """-> (mean over the samples of the entropy of the mean prediction over each sample's views [autograd],
+    softmax(z) [no grad] or None, info)"""
+    info = {}
+    loss = MarginalEntropyFn.apply(z.contiguous(), int(groups), int(views), bool(want_probs), info)
+    return loss, info.pop("probs"), info
+
+
 def argmax_ce(z):
     """-> (mean_r CE(z[r], argmax_k z[r]) (first maximum) [autograd], None, {}): the loss of the Fisher estimate"""
     R, K = z.shape
@@ -210,6 +263,7 @@ class TentState:
         base = flat._grads.data_ptr()
         self._slots = [self.grads[(t._gslot.data_ptr() - base) // 4:][:t.numel()].view(t.shape) for t in flat.tensors]
         self.source: Optional[List[torch.Tensor]] = None
+        self.views = None   # marginal_entropy_step's ImageAugmenter: reset() leaves its generator running, drop() forgets it
 
     @torch.no_grad()
     def snapshot(self):
@@ -330,6 +384,11 @@ def _state(model) -> TentState:
             model._tent = EataState(model.flat, names, model.hp.num_classes)
         else:
             model._tent = TentState(model.flat, names)
+        if model.hp.tta_method == "marginal_entropy":
+            from .augment import ImageAugmenter   # the torchvision-branch kernels: test images arrive as float CHW
+            hp = model.hp
+            model._tent.views = ImageAugmenter(img_size=hp.img_size, target=hp.target, kind=hp.tta_view_policy, augmentation_rate=1.0,
+                                               seed=hp.tta_view_seed, augmentation_speedup=False)
     return model._tent
 
 
@@ -477,6 +536,57 @@ def shot_im_step(model, batch):
         st.adam_step(hp.tta_lr)
         model.last_tta = dict(loss=loss, loss_entropy=info["loss_entropy"], loss_diversity=info["loss_diversity"],
                               marginal=info["marginal"], y_hat_m=out_m, probs=probs)
+        return model._score_test(probs, y)
+
+
+def make_views(model, x, draws=None):
+    """The views marginal_entropy_step adapts on, from the inputs x = (images [B, 3, H, W], table [B, C], ...) of a batch:
+    every image repeated tta_views times, sample-major (row g V + v is view v of sample g), and augmented by the model-owned
+    ImageAugmenter (family tta_view_policy, every row augmented, seeded by tta_view_seed when the adaptation state is created);
+    the table rows repeated UNCHANGED (the model holds no table to draw corrupted cells from).  draws: the host draws of an
+    earlier call (last_tta["draws"]), which rebuild its views bit for bit and leave the generator alone; None draws afresh.
+    -> (views [B V, 3, P, P], table [B V, C], draws)"""
+    if model.hp.tta_method != "marginal_entropy":
+        raise ValueError(f"augmented views belong to tta_method 'marginal_entropy' (this model: {model.hp.tta_method!r})")
+    with torch.inference_mode(False), torch.no_grad():
+        model.setup_device()
+        aug = _state(model).views
+        x_img, x_tab = _inputs(model, x)
+        V = model.hp.tta_views
+        B, _, H, W = x_img.shape
+        if draws is None:
+            draws = aug.draw(B * V, H, W)
+        views = aug(x_img.repeat_interleave(V, dim=0), draws, want_orig=False)[0]
+        return views, x_tab.repeat_interleave(V, dim=0), draws
+
+
+def marginal_entropy_step(model, batch):
+    """MEMO (Zhang, Levine, Finn, NeurIPS 2022) on one test batch of B samples, B = 1 being the case it is made for:
+    (1) V = tta_views augmented views of every sample (make_views); (2) the adapting pass on the B V rows with the loss
+    mean_g H(mean_v softmax(out_m[g V + v])), gradients for A only (no weight-gradient products), under tta_bn_prior = N at
+    rho = B V / (N + B V); (3) one Adam step over A; (4) the scores: the forward of bn_adapt_step on the CLEAN batch with the
+    updated A, at rho = B / (N + B).  This is the one method that scores after its update: with one sample and tta_episodic,
+    scores taken before it would show no adaptation at all.  With B > 1 the samples share one update, of the mean of their
+    marginal entropies.  MEMO as published is B = 1, tta_episodic: True, tta_bn_prior: 16, and adapts every parameter; here A is
+    the norm affines, as for every method.  State, Adam, episodic mode, reset and what is written are tent_step's; the views'
+    generator runs on through reset_tta() and episodes, and is dropped with the state by load_state_dict.
+    last_tta: loss, marginal [B, K], marginal_entropy [B] of the adapting pass, y_hat_m and probs [B, K] of the scoring
+    forward, all on the device, and draws, the host dict make_views rebuilds the views from."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        x_img, x_tab = _inputs(model, x)
+        B, V = x_img.shape[0], hp.tta_views
+        views, tab_rep, draws = make_views(model, (x_img, x_tab))
+        _, loss, _, info = adapting_pass(model, (views, tab_rep), st, lambda z: marginal_entropy(z, B, V))
+        st.adam_step(hp.tta_lr)
+        with torch.no_grad():
+            model.flat.refresh_layouts(student=True, teacher=False)
+            out_m = _forward(model, x_img, x_tab)
+            probs = ops.softmax_rows(out_m)
+        model.last_tta = dict(loss=loss, marginal=info["marginal"], marginal_entropy=info["marginal_entropy"], y_hat_m=out_m,
+                              probs=probs, draws=draws)
         return model._score_test(probs, y)
 
 
