@@ -33,3 +33,4 @@ extern "C" int stil_device_count(void) {
 #include "eata.hip"
 #include "infomax.hip"
 #include "margent.hip"
+#include "deyo.hip"

@@ -65,6 +65,14 @@ _DEFAULTS = dict(
     tta_views=32,                  # V: views per sample (the adapting pass runs on B x V rows)
     tta_view_policy="hard_eval",   # the transform family of the views: contrastive | hard_eval | soft_eval | weak | strong (augment._policy)
     tta_view_seed=2022,            # seed of the views' generator, which lives in the adaptation state
+    # "deyo" only: DeYO (Lee et al., ICLR 2024), entropy AND the drop of the predicted-class probability on a patch-shuffled second view
+    # (PLPD) decide which rows adapt the model.  The defaults are the paper's ImageNet-C values as recalled: unpinned
+    tta_patch_grid=4,              # the images are cut into grid x grid patches; must divide img_size
+    tta_ent_margin=None,           # tau_Ent: rows with entropy below it are reliable; None = 0.5 ln(num_classes)
+    tta_plpd_margin=0.2,           # tau_PLPD: reliable rows whose PLPD exceeds it are selected
+    tta_reweight_ent=1.0,          # weight of exp(E0 - H) in a selected row's weight (E0 = tta_e_margin; None = 0.4 ln(num_classes))
+    tta_reweight_plpd=1.0,         # weight of exp(PLPD) in it
+    tta_shuffle_seed=2024,         # seed of the permutations' generator, which lives in the adaptation state
 )
 
 
@@ -643,10 +651,12 @@ class STiLModel(_Base):
         tta.shot_im_step) and the scores
         are those of the adapting forward; with "bn_adapt" the scores are those of that forward and nothing is adapted.
         With "marginal_entropy" (tta.marginal_entropy_step, MEMO) the model adapts on tta_views augmented views of every sample
-        and the scores are those of a forward of the clean batch AFTER the update: the one method that scores after it."""
+        and the scores are those of a forward of the clean batch AFTER the update: the one method that scores after it.
+        With "deyo" (tta.deyo_step) a second, forward-only pass on the patch-shuffled images decides together with the entropy
+        which rows adapt the model; the scores are those of the clean adapting forward, before the update."""
         if self._tta_on():
             return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step,
-                    "marginal_entropy": tta.marginal_entropy_step}[self.hp.tta_method](self, batch)
+                    "marginal_entropy": tta.marginal_entropy_step, "deyo": tta.deyo_step}[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()

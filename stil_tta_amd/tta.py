@@ -1,6 +1,7 @@
 """Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
-al., ICML 2022), SHOT-IM (Liang et al., ICML 2020), MEMO's marginal entropy over augmented views (Zhang et al., NeurIPS 2022) and
-the forward-only "bn_adapt" baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
+al., ICML 2022), SHOT-IM (Liang et al., ICML 2020), MEMO's marginal entropy over augmented views (Zhang et al., NeurIPS 2022),
+DeYO's entropy-and-PLPD selection on a patch-shuffled second view (Lee et al., ICLR 2024) and the forward-only "bn_adapt"
+baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
 
 Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
     tent_step              entropy           -> Adam over A
@@ -8,10 +9,13 @@ Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatev
     shot_im_step           infomax           -> Adam over A
     marginal_entropy_step  marginal_entropy on V views of every sample (make_views) -> Adam over A -> the forward of
                            bn_adapt_step on the clean batch: the one method whose scores come after the update
+    deyo_step              the forward of bn_adapt_step on the patch-shuffled images (patch_shuffle), then deyo_entropy on the
+                           clean batch -> Adam over A gated by n > 0
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState`) lives in `model._tent`, and with
-it the augmenter of marginal_entropy_step's views (`TentState.views`).
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState`) lives in
+`model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
+shuffles (`DeyoState.rng`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ import contextlib
 import math
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -27,7 +32,7 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy")
+METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy", "deyo")
 PARAMS = ("bn", "norm")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
 
@@ -52,6 +57,20 @@ def check_hparams(hp):
         raise ValueError(f"Unknown tta_view_policy {hp.tta_view_policy!r}: valid are {VIEW_POLICIES}")
     if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:   # the generator takes no negative seed
         raise ValueError(f"tta_view_seed must be an int >= 0, not {seed!r}")
+    g = hp.tta_patch_grid
+    if isinstance(g, bool) or not isinstance(g, int) or g < 1 or hp.img_size % g != 0:
+        raise ValueError(f"tta_patch_grid must be an int >= 1 that divides img_size = {hp.img_size}, not {g!r}")
+    for name in ("tta_ent_margin", "tta_plpd_margin"):
+        v = getattr(hp, name)
+        if (v is not None or name == "tta_plpd_margin") and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v)):
+            raise ValueError(f"{name} must be {'None or ' if name == 'tta_ent_margin' else ''}a finite number, not {v!r}")
+    for name in ("tta_reweight_ent", "tta_reweight_plpd"):
+        v = getattr(hp, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+    seed = hp.tta_shuffle_seed
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"tta_shuffle_seed must be an int >= 0, not {seed!r}")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -145,6 +164,77 @@ def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=
     info = {}
     loss, p = EataEntropyFn.apply(z.contiguous(), e_margin, d_margin, momentum, m, m_valid, active, gate, info)
     return loss, p, info
+
+
+class DeyoFn(torch.autograd.Function):
+    """DeYO's loss (Lee et al., ICLR 2024) beside EataEntropyFn: (1/n) sum over the selected rows of w_r H_r, with z the logits
+    of the batch and zs those of its patch-shuffled images (no gradient).  plpd_r = p_r[yhat_r] - softmax(zs_r)[yhat_r], yhat_r
+    the first maximum of z_r; the selection (reliable: H_r < ent_margin; and plpd_r > plpd_margin), the weights w_r =
+    a_ent exp(e0 - H_r) + a_plpd exp(plpd_r) and the gate of the Adam step, all in stil_deyo_rows: n stays on the device.
+    -> (loss, probabilities); info = dict(H, plpd, w, yhat, rel, sel, counts [n, n_reliable, 0, 0], lse).
+    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient; w carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, zs, ent_margin, plpd_margin, e0, a_ent, a_plpd, active, gate, info):
+        _chk(z, zs, active, gate)
+        R, K = z.shape
+        if tuple(zs.shape) != (R, K):
+            raise ValueError(f"deyo_entropy: logits {tuple(z.shape)} against shuffled logits {tuple(zs.shape)}")
+        dev = z.device
+        lse, hd, wd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(3))
+        p = torch.empty_like(z)
+        h, d, w = (torch.empty((R,), dtype=torch.float32, device=dev) for _ in range(3))
+        yhat = torch.empty((R,), dtype=torch.int32, device=dev)
+        rel, sel = (torch.empty((R,), dtype=torch.uint8, device=dev) for _ in range(2))
+        dz = torch.empty_like(z)
+        counts = torch.empty((4,), dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nt = 0 if active is None else active.numel()
+        lib().deyo_rows(_p(z), K, _p(zs), K, R, K, float(ent_margin), float(plpd_margin), float(e0), float(a_ent), float(a_plpd), 1.0,
+                        _p(lse), _p(hd), _p(wd), _p(p), K, _p(h), _p(d), _p(w), _p(yhat), _p(rel), _p(sel), _p(dz), K, _p(counts),
+                        _p(loss), _p(active), _p(gate), nt, _stream())
+        info.update(H=h, plpd=d, w=w, yhat=yhat, rel=rel, sel=sel, counts=counts, lse=lse)
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return (_scale_by(dz, g),) + (None,) * 9
+
+
+def deyo_entropy(z, zs, ent_margin, plpd_margin, e0, a_ent=1.0, a_plpd=1.0, active=None, gate=None):
+    """-> (DeYO's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate."""
+    info = {}
+    loss, p = DeyoFn.apply(z.contiguous(), zs.detach().contiguous(), ent_margin, plpd_margin, e0, a_ent, a_plpd, active, gate, info)
+    return loss, p, info
+
+
+def patch_shuffle(x, grid, perm):
+    """DeYO's second view of the images x [B, C, H, W] (float32, on the device): every image cut into grid x grid patches and
+    patch slot s (row-major) filled with source patch perm[b, s], every channel alike (stil_patch_shuffle: a bit-exact copy).
+    perm: [B, grid^2] integers, a host array (numpy / CPU tensor: staged through pinned memory, no blocking copy) or an int32
+    device tensor; an entry outside [0, grid^2) leaves its slot in place.  -> the shuffled images (a new tensor)"""
+    _chk(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"patch_shuffle: images must be float32 [B, C, H, W], not {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    grid = int(grid)
+    if grid < 1 or H % grid or W % grid:
+        raise ValueError(f"patch_shuffle: grid = {grid} must divide H = {H} and W = {W}")
+    if not torch.is_tensor(perm):
+        perm = torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int32))
+    if tuple(perm.shape) != (B, grid * grid):
+        raise ValueError(f"patch_shuffle: perm of shape {tuple(perm.shape)} for {B} images of {grid * grid} patches")
+    if perm.device != x.device:
+        perm = perm.to(torch.int32).contiguous().pin_memory().to(x.device, non_blocking=True)
+    elif perm.dtype != torch.int32 or not perm.is_contiguous():
+        perm = perm.to(torch.int32).contiguous()
+    out = torch.empty_like(x)
+    lib().patch_shuffle(_p(x), _p(out), B, C, H, W, grid, _p(perm), _stream())
+    return out
 
 
 class InfoMaxFn(torch.autograd.Function):
@@ -376,12 +466,51 @@ class EataState(TentState):
         torch._foreach_copy_(views, [t.detach().to(self.fisher.device, torch.float32) for t in tensors])
 
 
+def draw_perm(rng: np.random.Generator, B: int, grid: int) -> np.ndarray:
+    """-> int32 [B, grid^2]: one uniform permutation of the patch slots per image, drawn from `rng`"""
+    return rng.permuted(np.tile(np.arange(grid * grid, dtype=np.int32), (B, 1)), axis=1)
+
+
+class DeyoState(TentState):
+    """TentState plus what DeYO adds (Lee et al., ICLR 2024): the gated copy of the Adam mask (`gate` = active and n > 0,
+    written by stil_deyo_rows) and the host generator of the patch permutations, seeded once: reset() leaves it running,
+    drop() forgets it."""
+
+    def __init__(self, flat: FlatState, names: List[str], seed: int):
+        super().__init__(flat, names)
+        self.gate = torch.zeros_like(self.active)
+        self.rng = np.random.default_rng(seed)
+
+        self._pin = None    # the pinned staging buffer of the permutations and the event of its last upload
+        self._pin_done = None
+
+    def draw(self, B: int, grid: int) -> np.ndarray:
+        return draw_perm(self.rng, B, grid)
+
+    def upload(self, perm: np.ndarray) -> torch.Tensor:
+        """perm (host, int32 [B, grid^2]) -> a device tensor, staged through this state's pinned buffer by a non-blocking copy.
+        The buffer is rewritten only once its previous upload has run (an event query; a wait only if the device is more than
+        a whole step behind the host)."""
+        src = torch.from_numpy(perm)
+        if self._pin is None or self._pin.shape != src.shape:
+            self._pin, self._pin_done = torch.empty(src.shape, dtype=torch.int32).pin_memory(), None
+        if self._pin_done is not None and not self._pin_done.query():
+            self._pin_done.synchronize()
+        self._pin.copy_(src)
+        out = self._pin.to(self.active.device, non_blocking=True)
+        self._pin_done = torch.cuda.Event()
+        self._pin_done.record()
+        return out
+
+
 def _state(model) -> TentState:
     """model._tent, created on first use (the model is on its device)"""
     if model._tent is None:
         names = [n[len("model."):] for n in param_names(model)]   # FlatState names the backbone's own parameters
         if model.hp.tta_method == "eata":
             model._tent = EataState(model.flat, names, model.hp.num_classes)
+        elif model.hp.tta_method == "deyo":
+            model._tent = DeyoState(model.flat, names, model.hp.tta_shuffle_seed)
         else:
             model._tent = TentState(model.flat, names)
         if model.hp.tta_method == "marginal_entropy":
@@ -587,6 +716,44 @@ def marginal_entropy_step(model, batch):
             probs = ops.softmax_rows(out_m)
         model.last_tta = dict(loss=loss, marginal=info["marginal"], marginal_entropy=info["marginal_entropy"], y_hat_m=out_m,
                               probs=probs, draws=draws)
+        return model._score_test(probs, y)
+
+
+def deyo_step(model, batch):
+    """DeYO (Lee et al., ICLR 2024) on one test batch: (1) one permutation of the tta_patch_grid^2 patch slots per image, drawn
+    on the host from the state's generator (seeded by tta_shuffle_seed when the adaptation state is created; it runs on through
+    reset_tta() and episodes and is dropped with the state by load_state_dict), checked to be a permutation and uploaded
+    from the state's pinned buffer without a blocking copy; (2) the forward of bn_adapt_step on the patch-shuffled images and the UNCHANGED table, under
+    no_grad: zs; (3) TENT's forward and input-gradient-only backward on the clean batch with the loss restricted to the rows
+    with H_r < tta_ent_margin and plpd_r = p_r[yhat_r] - softmax(zs_r)[yhat_r] > tta_plpd_margin, weighted by
+    tta_reweight_ent exp(E0 - H_r) + tta_reweight_plpd exp(plpd_r) (E0 = tta_e_margin) and averaged over the n selected rows;
+    (4) one Adam step over A if and only if n > 0: n, the counts and that gate stay on the device, the step reads nothing back.
+    Unlike the published code, (2) runs on ALL B rows, not only the entropy-reliable ones: shapes stay fixed and nothing is
+    read back; its BatchNorm therefore uses the statistics of the whole shuffled batch (under tta_bn_prior like every
+    adapting forward).  Writes what tent_step writes.  The scores are softmax(out_m) of the clean forward, before the update.
+    last_tta: loss, n_selected, n_reliable, entropy, plpd, weight, reliable, selected, y_hat_m, probs, y_hat_shuffled (zs), all
+    on the device, and perm, the host array patch_shuffle rebuilds the shuffled batch from."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        x_img, x_tab = _inputs(model, x)
+        g = hp.tta_patch_grid
+        perm = st.draw(x_img.shape[0], g)
+        if not np.array_equal(np.sort(perm, axis=1), np.broadcast_to(np.arange(g * g, dtype=np.int32), perm.shape)):
+            raise RuntimeError("deyo_step: a drawn row is not a permutation of the patch slots")
+        lnk = math.log(hp.num_classes)
+        tau = 0.5 * lnk if hp.tta_ent_margin is None else float(hp.tta_ent_margin)
+        e0 = 0.4 * lnk if hp.tta_e_margin is None else float(hp.tta_e_margin)
+        with torch.no_grad():
+            model.flat.refresh_layouts(student=True, teacher=False)
+            zs = _forward(model, patch_shuffle(x_img, g, st.upload(perm)), x_tab)
+        out_m, loss, probs, info = adapting_pass(model, (x_img, x_tab), st, lambda z: deyo_entropy(
+            z, zs, tau, hp.tta_plpd_margin, e0, hp.tta_reweight_ent, hp.tta_reweight_plpd, st.active, st.gate))
+        st.adam_step(hp.tta_lr, mask=st.gate)
+        model.last_tta = dict(loss=loss, n_selected=info["counts"][0], n_reliable=info["counts"][1], entropy=info["H"],
+                              plpd=info["plpd"], weight=info["w"], reliable=info["rel"], selected=info["sel"], y_hat_m=out_m,
+                              probs=probs, y_hat_shuffled=zs, perm=perm)
         return model._score_test(probs, y)
 
 
