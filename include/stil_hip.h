@@ -216,6 +216,11 @@ int stil_attention_fwd(const float* qkv, float* out, float* probs, const unsigne
 int stil_attention_bwd(const float* dout, const float* qkv, const float* probs, const unsigned char* mask,
                        float* dqkv, int B, int T, int H, int d, int q_off, int Sq, int kv_off, int Skv,
                        float scale, float drop_p, void* stream);
+/* the kernel stil_attention_fwd (bwd == 0) / stil_attention_bwd (bwd != 0) launches for a window of Sq queries and Skv keys at
+ * head dim d: 0 = the VALU kernel, 1 = the matrix-pipe kernel with 256 threads, 2 = the one with 512 threads, < 0 = the entry
+ * point refuses the shape (head dim not a positive multiple of 4, an empty window, or no kernel fits 160 KiB of LDS).  Computed
+ * by the launchers' own selection; host only, no GPU call.  A shape the forward takes may be one the backward refuses. */
+int stil_attention_config(int Sq, int Skv, int d, int bwd);
 /* kind 1: dx = dy*(ref>0) (ref = ReLU output); kind 2: dx = dy*gelu'(ref) (ref = pre-activation) */
 int stil_act_bwd(const float* dy, const float* ref, float* dx, long n, int kind, void* stream);
 /* out = resid + x * emask[i] * rmask[i/rowlen] * scale   (nn.Dropout / drop_path / residual add) */

@@ -833,6 +833,29 @@ static bool attn_mfma_ok(int Sq, int Skv, int d, size_t lds) {
 // 8 waves per (batch, head) once the score matrix has >= 16 tiles of 16 x 16
 static bool attn_big_wg(int Sq, int Skv) { return (attn_up16(Sq) >> 4) * (attn_up16(Skv) >> 4) >= 16; }
 
+// The one selection rule of the attention launchers (stil_attention_config reports it): kernel 0 = VALU, 1 = matrix pipe with
+// 256 threads, 2 = matrix pipe with 512 threads, < 0 = no kernel fits 160 KiB of LDS; lds = dynamic LDS of that kernel (of the
+// VALU kernel where none fits).  Matrix-pipe kernel unless it would keep fewer workgroups resident than the VALU kernel (both
+// are latency-bound); 8-wave matrix-pipe workgroups have twice the waves of the VALU kernel's even at one workgroup fewer.
+struct AttnPlan { int kernel; size_t lds; };
+static AttnPlan attn_plan(int Sq, int Skv, int d, bool bwd) {
+  const int Smax = Sq > Skv ? Sq : Skv;
+  const size_t lds = bwd ? ((size_t)2 * Smax * (d + 4) + (size_t)2 * Sq * Skv) * sizeof(float)
+                         : ((size_t)Sq * d + (size_t)Skv * (d + 4) + (size_t)Sq * Skv) * sizeof(float);
+  const size_t lds_m = attn_mfma_lds(Sq, Skv, d, bwd);   // MFMA path: d % 16 == 0 and its padded tiles fit
+  const bool big = attn_big_wg(Sq, Skv);
+  const bool mfma = attn_mfma_ok(Sq, Skv, d, lds_m) && (lds > 160 * 1024 || big || (160 * 1024) / lds_m >= (160 * 1024) / lds);
+  AttnPlan pl;
+  pl.kernel = mfma ? (big ? 2 : 1) : (lds <= 160 * 1024 ? 0 : STIL_EINVAL);
+  pl.lds = mfma ? lds_m : lds;
+  return pl;
+}
+
+extern "C" int stil_attention_config(int Sq, int Skv, int d, int bwd) {
+  if (d % 4 != 0 || d <= 0 || Sq <= 0 || Skv <= 0) return STIL_EINVAL;   // attn_check's conditions on the shape
+  return attn_plan(Sq, Skv, d, bwd != 0).kernel;
+}
+
 static bool g_attn_attr_set = false;
 static int attn_set_attr() {
   if (g_attn_attr_set) return STIL_OK;
@@ -856,20 +879,16 @@ extern "C" int stil_attention_fwd(const float* qkv, float* out, float* probs, co
   STIL_REQUIRE(qkv && out && probs, "stil_attention_fwd: null pointer");
   int rc = attn_check(T, H, d, q_off, Sq, kv_off, Skv);
   if (rc) return rc;
-  size_t lds = ((size_t)Sq * d + (size_t)Skv * (d + 4) + (size_t)Sq * Skv) * sizeof(float);
-  const size_t lds_m = attn_mfma_lds(Sq, Skv, d, false);   // MFMA path: d % 16 == 0 and its padded tiles fit
-  // matrix-pipe kernel unless it would keep fewer workgroups resident than the VALU kernel (both are latency-bound)
-  const bool big = attn_big_wg(Sq, Skv);   // 8-wave matrix-pipe workgroups: twice the waves of the VALU kernel's even at one workgroup fewer
-  const bool mfma = attn_mfma_ok(Sq, Skv, d, lds_m) && (lds > 160 * 1024 || big || (160 * 1024) / lds_m >= (160 * 1024) / lds);
-  STIL_REQUIRE(mfma || lds <= 160 * 1024, "stil_attention_fwd: needs %zu B of LDS (> 160 KiB): Sq=%d Skv=%d d=%d", lds, Sq, Skv, d);
+  const AttnPlan pl = attn_plan(Sq, Skv, d, false);
+  STIL_REQUIRE(pl.kernel >= 0, "stil_attention_fwd: needs %zu B of LDS (> 160 KiB): Sq=%d Skv=%d d=%d", pl.lds, Sq, Skv, d);
   if ((rc = attn_set_attr())) return rc;
   AttnArgs p;
   p.qkv = qkv; p.out = out; p.probs = probs; p.mask = mask; p.dout = nullptr; p.dqkv = nullptr;
   p.B = B; p.T = T; p.H = H; p.d = d; p.q_off = q_off; p.Sq = Sq; p.kv_off = kv_off; p.Skv = Skv;
   p.scale = scale; p.drop_scale = mask ? 1.f / (1.f - drop_p) : 1.f;
-  if (mfma && big) hipLaunchKernelGGL(attn_fwd_mfma_kernel<512>, dim3(B * H), dim3(512), lds_m, (hipStream_t)stream, p);
-  else if (mfma) hipLaunchKernelGGL(attn_fwd_mfma_kernel<256>, dim3(B * H), dim3(256), lds_m, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H), dim3(256), lds, (hipStream_t)stream, p);
+  if (pl.kernel == 2) hipLaunchKernelGGL(attn_fwd_mfma_kernel<512>, dim3(B * H), dim3(512), pl.lds, (hipStream_t)stream, p);
+  else if (pl.kernel == 1) hipLaunchKernelGGL(attn_fwd_mfma_kernel<256>, dim3(B * H), dim3(256), pl.lds, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H), dim3(256), pl.lds, (hipStream_t)stream, p);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
@@ -880,21 +899,16 @@ extern "C" int stil_attention_bwd(const float* dout, const float* qkv, const flo
   STIL_REQUIRE(dout && qkv && probs && dqkv, "stil_attention_bwd: null pointer");
   int rc = attn_check(T, H, d, q_off, Sq, kv_off, Skv);
   if (rc) return rc;
-  int Smax = Sq > Skv ? Sq : Skv;
-  size_t lds = ((size_t)2 * Smax * (d + 4) + (size_t)2 * Sq * Skv) * sizeof(float);
-  const size_t lds_m = attn_mfma_lds(Sq, Skv, d, true);
-  // matrix-pipe kernel unless it would keep fewer workgroups resident than the VALU kernel (both are latency-bound)
-  const bool big = attn_big_wg(Sq, Skv);
-  const bool mfma = attn_mfma_ok(Sq, Skv, d, lds_m) && (lds > 160 * 1024 || big || (160 * 1024) / lds_m >= (160 * 1024) / lds);
-  STIL_REQUIRE(mfma || lds <= 160 * 1024, "stil_attention_bwd: needs %zu B of LDS (> 160 KiB)", lds);
+  const AttnPlan pl = attn_plan(Sq, Skv, d, true);
+  STIL_REQUIRE(pl.kernel >= 0, "stil_attention_bwd: needs %zu B of LDS (> 160 KiB): Sq=%d Skv=%d d=%d", pl.lds, Sq, Skv, d);
   if ((rc = attn_set_attr())) return rc;
   AttnArgs p;
   p.qkv = qkv; p.out = nullptr; p.probs = const_cast<float*>(probs); p.mask = mask; p.dout = dout; p.dqkv = dqkv;
   p.B = B; p.T = T; p.H = H; p.d = d; p.q_off = q_off; p.Sq = Sq; p.kv_off = kv_off; p.Skv = Skv;
   p.scale = scale; p.drop_scale = mask ? 1.f / (1.f - drop_p) : 1.f;
-  if (mfma && big) hipLaunchKernelGGL(attn_bwd_mfma_kernel<512>, dim3(B * H), dim3(512), lds_m, (hipStream_t)stream, p);
-  else if (mfma) hipLaunchKernelGGL(attn_bwd_mfma_kernel<256>, dim3(B * H), dim3(256), lds_m, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H), dim3(256), lds, (hipStream_t)stream, p);
+  if (pl.kernel == 2) hipLaunchKernelGGL(attn_bwd_mfma_kernel<512>, dim3(B * H), dim3(512), pl.lds, (hipStream_t)stream, p);
+  else if (pl.kernel == 1) hipLaunchKernelGGL(attn_bwd_mfma_kernel<256>, dim3(B * H), dim3(256), pl.lds, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H), dim3(256), pl.lds, (hipStream_t)stream, p);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

@@ -1048,11 +1048,16 @@ class AttentionFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, qkv, H, windows, masks, drop_p):
+    def forward(ctx, qkv, H, windows, masks, drop_p, needs_bwd=True):
         _chk(qkv)
         B, T, three = qkv.shape
         d = three // (3 * H)
         scale = d ** -0.5
+        if needs_bwd and qkv.requires_grad:   # a window the backward kernels refuse fails here, before the forward is paid for
+            for qo, Sq, ko, Skv in windows:
+                if lib().attention_config(Sq, Skv, d, 1) < 0:
+                    raise RuntimeError(f"stil_attention_bwd would refuse this window (no backward kernel fits 160 KiB of LDS, or a bad "
+                                       f"shape): Sq={Sq} Skv={Skv} d={d}; run it under torch.no_grad() if no gradient is needed")
         covered = sum(w_[1] for w_ in windows) == T  # query windows are disjoint: every output row written once
         out = (torch.empty if covered else torch.zeros)((B, T, H * d), dtype=torch.float32, device=qkv.device)
         probs = []
@@ -1077,11 +1082,12 @@ class AttentionFn(torch.autograd.Function):
             mk = None if masks is None else masks[wi]
             lib().attention_bwd(_p(gout), _p(qkv), _p(probs[wi]), _p(mk), _p(dqkv), B, T, H, d, qo, Sq, ko, Skv, scale,
                                 drop_p, _stream())
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None
 
 
 def attention(qkv, H, windows, masks=None, drop_p=0.0):
-    return AttentionFn.apply(qkv, H, tuple(windows), masks, drop_p)
+    # grad mode is off inside forward(), so whether a backward can follow is decided here
+    return AttentionFn.apply(qkv, H, tuple(windows), masks, drop_p, torch.is_grad_enabled())
 
 
 class DropAddFn(torch.autograd.Function):

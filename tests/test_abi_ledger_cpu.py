@@ -25,6 +25,8 @@ _AUG = "test_gpu_augment.py"
 _ALB = "test_gpu_augment_alb.py"
 _MATCH = "test_gpu_match.py"
 _MET = "test_gpu_metrics.py"
+_ATT = "test_gpu_attention.py"
+_ATT_CPU = "test_attention_config_cpu.py"
 
 # name -> list of "file::function" (checked directly there) | str (the reason it has no test of its own)
 LEDGER = {
@@ -72,8 +74,13 @@ LEDGER = {
     "stil_layernorm_bwd_workspace_bytes": "size of the per-block partials of stil_layernorm_bwd, whose block count is internal; a short workspace is "
                                           "rejected inside test_layernorm",
     "stil_layernorm_bwd": [f"{OPS}::test_layernorm"],
-    "stil_attention_fwd": [f"{OPS}::test_attention"],
-    "stil_attention_bwd": [f"{OPS}::test_attention"],
+    "stil_attention_fwd": [f"{_ATT}::test_attention_kernels_against_float64", f"{_ATT}::test_every_kernel_is_reached_in_every_orientation",
+                           f"{OPS}::test_attention"],
+    "stil_attention_bwd": [f"{_ATT}::test_attention_kernels_against_float64", f"{_ATT}::test_refused_backward_launches_nothing",
+                           f"{OPS}::test_attention"],
+    "stil_attention_config": [f"{_ATT_CPU}::test_the_cases_of_the_gpu_test_map_to_their_kernels",
+                              f"{_ATT_CPU}::test_config_is_negative_exactly_where_the_entry_points_refuse",
+                              f"{_ATT_CPU}::test_the_shapes_forward_takes_and_backward_refuses_are_pinned"],
     "stil_act_bwd": [f"{EP}::test_act_bwd"],
     "stil_drop_add": [f"{EP}::test_drop_add_both_paths_all_operand_combinations", f"{EP}::test_drop_add_vector_and_scalar_paths_agree_bit_for_bit",
                       f"{EP}::test_drop_add_backward"],
