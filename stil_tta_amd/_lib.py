@@ -1,5 +1,5 @@
 """ctypes binding of libstil_hip.so, generated from include/stil_hip.h, include/stil_tta.h, include/stil_eata.h,
-include/stil_bnprior.h, include/stil_infomax.h, include/stil_margent.h and include/stil_deyo.h at import time.
+include/stil_bnprior.h, include/stil_infomax.h, include/stil_margent.h, include/stil_deyo.h and include/stil_sar.h at import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -20,6 +20,7 @@ BNPRIOR_HEADER = os.path.join(_ROOT, "include", "stil_bnprior.h")  # test-time B
 INFOMAX_HEADER = os.path.join(_ROOT, "include", "stil_infomax.h")  # SHOT's information-maximisation loss (a ledger of its own)
 MARGENT_HEADER = os.path.join(_ROOT, "include", "stil_margent.h")  # MEMO's marginal entropy over augmented views (a ledger of its own)
 DEYO_HEADER = os.path.join(_ROOT, "include", "stil_deyo.h")  # DeYO: the patch-shuffled view and the PLPD selection (a ledger of its own)
+SAR_HEADER = os.path.join(_ROOT, "include", "stil_sar.h")  # SAR: the two-pass row loss, the ascent step and the model recovery (a ledger of its own)
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -98,6 +99,7 @@ class _Lib:
         self.protos.update(parse_header(INFOMAX_HEADER))
         self.protos.update(parse_header(MARGENT_HEADER))
         self.protos.update(parse_header(DEYO_HEADER))
+        self.protos.update(parse_header(SAR_HEADER))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks
             fn.restype = restype

@@ -34,3 +34,4 @@ extern "C" int stil_device_count(void) {
 #include "infomax.hip"
 #include "margent.hip"
 #include "deyo.hip"
+#include "sar.hip"

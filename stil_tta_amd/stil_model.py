@@ -73,6 +73,10 @@ _DEFAULTS = dict(
     tta_reweight_ent=1.0,          # weight of exp(E0 - H) in a selected row's weight (E0 = tta_e_margin; None = 0.4 ln(num_classes))
     tta_reweight_plpd=1.0,         # weight of exp(PLPD) in it
     tta_shuffle_seed=2024,         # seed of the permutations' generator, which lives in the adaptation state
+    # "sar" only: SAR (Niu et al., ICLR 2023), the entropy of the rows below tta_e_margin minimised at A + rho g / |g|, with model recovery
+    tta_sar_rho=0.05,              # rho: the radius of the ascent step over A between the two passes (the paper's default); 0: no perturbation
+    tta_sar_reset=None,            # A returns to its source values when the running mean of the loss falls below it; None = 0.2 ln(num_classes) / ln(1000)
+                                   # (the paper's ImageNet 0.2 at the same fraction of the maximal entropy: this project's scaling); False: no recovery
 )
 
 
@@ -653,10 +657,12 @@ class STiLModel(_Base):
         With "marginal_entropy" (tta.marginal_entropy_step, MEMO) the model adapts on tta_views augmented views of every sample
         and the scores are those of a forward of the clean batch AFTER the update: the one method that scores after it.
         With "deyo" (tta.deyo_step) a second, forward-only pass on the patch-shuffled images decides together with the entropy
-        which rows adapt the model; the scores are those of the clean adapting forward, before the update."""
+        which rows adapt the model; the scores are those of the clean adapting forward, before the update.
+        With "sar" (tta.sar_step) the batch runs two adapting passes, the second at A + tta_sar_rho g / |g|, and A recovers its
+        source values when the running mean of the loss falls below tta_sar_reset; the scores are the first pass's."""
         if self._tta_on():
             return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step,
-                    "marginal_entropy": tta.marginal_entropy_step, "deyo": tta.deyo_step}[self.hp.tta_method](self, batch)
+                    "marginal_entropy": tta.marginal_entropy_step, "deyo": tta.deyo_step, "sar": tta.sar_step}[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()

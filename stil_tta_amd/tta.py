@@ -1,9 +1,10 @@
 """Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
 al., ICML 2022), SHOT-IM (Liang et al., ICML 2020), MEMO's marginal entropy over augmented views (Zhang et al., NeurIPS 2022),
-DeYO's entropy-and-PLPD selection on a patch-shuffled second view (Lee et al., ICLR 2024) and the forward-only "bn_adapt"
-baseline, optionally under a source-statistics BatchNorm prior (tta_bn_prior).
+DeYO's entropy-and-PLPD selection on a patch-shuffled second view (Lee et al., ICLR 2024), SAR's sharpness-aware two-pass
+entropy steps with model recovery (Niu et al., ICLR 2023) and the forward-only "bn_adapt" baseline, optionally under a
+source-statistics BatchNorm prior (tta_bn_prior).
 
-Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
+Every method but SAR is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
     tent_step              entropy           -> Adam over A
     eata_step              eata_entropy      -> Fisher anchor (when an estimate is loaded) -> Adam over A gated by n > 0
     shot_im_step           infomax           -> Adam over A
@@ -11,9 +12,11 @@ Every method is ONE adapting pass (`adapting_pass`) with its own loss and whatev
                            bn_adapt_step on the clean batch: the one method whose scores come after the update
     deyo_step              the forward of bn_adapt_step on the patch-shuffled images (patch_shuffle), then deyo_entropy on the
                            clean batch -> Adam over A gated by n > 0
+    sar_step               sar_entropy -> A + rho g / |g| -> sar_entropy again on the rows the first pass kept -> A restored ->
+                           Adam over A gated by n > 0 -> recovery of A when the running mean of the loss falls below tta_sar_reset
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState`) lives in
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState`) lives in
 `model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
 shuffles (`DeyoState.rng`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
@@ -32,7 +35,7 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy", "deyo")
+METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy", "deyo", "sar")
 PARAMS = ("bn", "norm")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
 
@@ -71,6 +74,11 @@ def check_hparams(hp):
     seed = hp.tta_shuffle_seed
     if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
         raise ValueError(f"tta_shuffle_seed must be an int >= 0, not {seed!r}")
+    rho, c = hp.tta_sar_rho, hp.tta_sar_reset
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not math.isfinite(rho) or rho < 0:
+        raise ValueError(f"tta_sar_rho must be a finite number >= 0, not {rho!r}")
+    if c is not None and c is not False and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0):
+        raise ValueError(f"tta_sar_reset must be None, False or a finite number > 0, not {c!r}")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -208,6 +216,50 @@ def deyo_entropy(z, zs, ent_margin, plpd_margin, e0, a_ent=1.0, a_plpd=1.0, acti
     """-> (DeYO's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate."""
     info = {}
     loss, p = DeyoFn.apply(z.contiguous(), zs.detach().contiguous(), ent_margin, plpd_margin, e0, a_ent, a_plpd, active, gate, info)
+    return loss, p, info
+
+
+class SarEntropyFn(torch.autograd.Function):
+    """SAR's loss (Niu et al., ICLR 2023) beside EataEntropyFn: (1/n) sum over the selected rows of H_r, unweighted; a row is
+    selected when H_r < margin and, in the second pass, the first pass selected it too (`prior`, its `sel`).  With `ema` (the
+    second pass) the running mean of the loss and the recovery flag are updated as well, all in stil_sar_rows: n, the gate of
+    the Adam step and the recovery decision stay on the device.
+    -> (loss, probabilities); info = dict(H, sel, counts [n, rows with H < margin, rows the prior admits, 0], lse).
+    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, z, margin, prior, active, gate, ema, ema_valid, momentum, reset, recover, info):
+        _chk(z, prior, active, gate, ema, ema_valid, recover)
+        R, K = z.shape
+        if prior is not None and (prior.dtype != torch.uint8 or prior.numel() != R):
+            raise ValueError(f"sar_entropy: a prior selection of {prior.numel()} {prior.dtype} entries for {R} rows")
+        dev = z.device
+        lse, hd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
+        p = torch.empty_like(z)
+        h = torch.empty((R,), dtype=torch.float32, device=dev)
+        sel = torch.empty((R,), dtype=torch.uint8, device=dev)
+        dz = torch.empty_like(z)
+        counts = torch.empty((4,), dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nt = 0 if active is None else active.numel()
+        lib().sar_rows(_p(z), K, R, K, float(margin), 1.0, _p(prior), _p(lse), _p(hd), _p(p), K, _p(h), _p(sel), _p(dz), K, _p(counts),
+                       _p(loss), _p(active), _p(gate), nt, _p(ema), _p(ema_valid), float(momentum), float(reset), _p(recover), _stream())
+        info.update(H=h, sel=sel, counts=counts, lse=lse)
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, g, _gp=None):
+        (dz,) = ctx.saved_tensors
+        return (_scale_by(dz, g),) + (None,) * 10
+
+
+def sar_entropy(z, margin, prior=None, active=None, gate=None, ema=None, ema_valid=None, momentum=0.9, reset=0.0, recover=None):
+    """-> (the mean entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate, and with `ema` the
+    running mean of the loss (ema, ema_valid) and the recovery flag (reset <= 0: never raised)."""
+    info = {}
+    loss, p = SarEntropyFn.apply(z.contiguous(), margin, prior, active, gate, ema, ema_valid, momentum, reset, recover, info)
     return loss, p, info
 
 
@@ -393,14 +445,13 @@ class TentState:
                         float(eps), 0.0, 1.0, _stream())
 
 
-class EataState(TentState):
-    """TentState plus what EATA adds (Niu et al., ICML 2022): the running mean `m` [K] of the selected predictions and its
-    validity flag, the gated copy of the Adam mask (`gate` = active and n > 0, written by stil_eata_rows), and the Fisher
-    estimate.  Fisher and source values are COMPACT: `achunks` lists the 1024-float slab chunks of A, chunk j of `fisher` /
-    `theta0` belongs to slab chunk achunks[j] (`source` holds views into `theta0`, so reset() restores as TentState's).  For A =
-    the 106 BatchNorm affines of a ResNet-50 that is 114 chunks: 456 KiB each, against 178 MiB for a slab in the flat layout."""
+class CompactState(TentState):
+    """TentState with the source values held COMPACT, the layout EataState and SarState share: `achunks` lists the 1024-float
+    slab chunks of A, chunk j of `theta0` (and of every buffer built like it) belongs to slab chunk achunks[j]; `source` holds
+    views into `theta0`, so reset() restores as TentState's.  For A = the 106 BatchNorm affines of a ResNet-50 that is 114
+    chunks: 456 KiB per buffer, against 178 MiB for a slab in the flat layout."""
 
-    def __init__(self, flat: FlatState, names: List[str], num_classes: int):
+    def __init__(self, flat: FlatState, names: List[str]):
         super().__init__(flat, names)
         dev = flat.params.device
         base = flat.params.data_ptr()
@@ -412,11 +463,6 @@ class EataState(TentState):
         self.n_achunks = len(chunks)
         self.achunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
         self.theta0 = torch.zeros(self.n_achunks * ALIGN, dtype=torch.float32, device=dev)
-        self.fisher: Optional[torch.Tensor] = None
-        self.partial = torch.zeros(max(self.n_achunks, 1), dtype=torch.float64, device=dev)
-        self.m = torch.zeros(num_classes, dtype=torch.float32, device=dev)
-        self.m_valid = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.gate = torch.zeros_like(self.active)
 
     def _compact_views(self, buf):
         return [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._spans, self.tensors)]
@@ -425,6 +471,21 @@ class EataState(TentState):
     def snapshot(self):
         self.source = self._compact_views(self.theta0)
         torch._foreach_copy_(self.source, [t.detach() for t in self.tensors])
+
+
+class EataState(CompactState):
+    """CompactState plus what EATA adds (Niu et al., ICML 2022): the running mean `m` [K] of the selected predictions and its
+    validity flag, the gated copy of the Adam mask (`gate` = active and n > 0, written by stil_eata_rows), and the Fisher
+    estimate, compact like the source values."""
+
+    def __init__(self, flat: FlatState, names: List[str], num_classes: int):
+        super().__init__(flat, names)
+        dev = flat.params.device
+        self.fisher: Optional[torch.Tensor] = None
+        self.partial = torch.zeros(max(self.n_achunks, 1), dtype=torch.float64, device=dev)
+        self.m = torch.zeros(num_classes, dtype=torch.float32, device=dev)
+        self.m_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gate = torch.zeros_like(self.active)
 
     @torch.no_grad()
     def reset(self):
@@ -464,6 +525,57 @@ class EataState(TentState):
             if tuple(v.shape) != tuple(t.shape):
                 raise ValueError(f"Fisher estimate of shape {tuple(t.shape)} for a parameter of shape {tuple(v.shape)}")
         torch._foreach_copy_(views, [t.detach().to(self.fisher.device, torch.float32) for t in tensors])
+
+
+class SarState(CompactState):
+    """CompactState plus what SAR adds (Niu et al., ICLR 2023): `saved` (A before the ascent step) and `e` (the ascent step
+    rho g / |g|), compact like the source values and readable until the next step; `norm` (|g|, double) and its per-chunk
+    scratch `partial`; the gated copy of the Adam mask (`gate` = active and n2 > 0, written by stil_sar_rows); `sel1`, the first
+    pass's selection of the latest batch; the running mean of the second pass's loss (`ema`, `ema_valid`) and the recovery flag
+    (`recover`), all on the device."""
+
+    def __init__(self, flat: FlatState, names: List[str]):
+        super().__init__(flat, names)
+        dev = flat.params.device
+        self.saved = torch.zeros_like(self.theta0)
+        self.e = torch.zeros_like(self.theta0)
+        self.partial = torch.zeros(max(self.n_achunks, 1), dtype=torch.float64, device=dev)
+        self.norm = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.gate = torch.zeros_like(self.active)
+        self.sel1: Optional[torch.Tensor] = None
+        self.ema = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.ema_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.recover = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    @torch.no_grad()
+    def reset(self):
+        """TentState.reset, and the running mean of the loss is forgotten too."""
+        super().reset()
+        self.ema.zero_()
+        self.ema_valid.zero_()
+        self.recover.zero_()
+
+    def _slab_args(self):
+        f = self.flat
+        return _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total
+
+    @torch.no_grad()
+    def perturb(self, rho: float):
+        """norm <- |grads| over A; saved <- A; e <- rho grads / (norm + 1e-12); A <- A + e"""
+        lib().sar_perturb(_p(self.flat.params), _p(self.grads), _p(self.saved), _p(self.e), *self._slab_args(), float(rho),
+                          _p(self.partial), _p(self.norm), _stream())
+
+    @torch.no_grad()
+    def restore(self):
+        """A <- saved, a copy"""
+        lib().sar_restore(_p(self.flat.params), _p(self.saved), *self._slab_args(), _stream())
+
+    @torch.no_grad()
+    def recover_if_flagged(self):
+        """When `recover` is set: A <- its source values, moments and step counts cleared, the running mean forgotten; decided
+        on the device, nothing is written otherwise."""
+        lib().sar_recover(_p(self.flat.params), _p(self.theta0), _p(self.exp_avg), _p(self.exp_avg_sq), _p(self.steps),
+                          *self._slab_args(), _p(self.recover), _p(self.ema_valid), _stream())
 
 
 def draw_perm(rng: np.random.Generator, B: int, grid: int) -> np.ndarray:
@@ -511,6 +623,8 @@ def _state(model) -> TentState:
             model._tent = EataState(model.flat, names, model.hp.num_classes)
         elif model.hp.tta_method == "deyo":
             model._tent = DeyoState(model.flat, names, model.hp.tta_shuffle_seed)
+        elif model.hp.tta_method == "sar":
+            model._tent = SarState(model.flat, names)
         else:
             model._tent = TentState(model.flat, names)
         if model.hp.tta_method == "marginal_entropy":
@@ -549,7 +663,7 @@ def drop(model):
 def reset(model):
     """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset),
     moments and step counts cleared; the next adapted batch takes the source values afresh.  EATA: the running mean of
-    the selected predictions is cleared too, the Fisher estimate is kept."""
+    the selected predictions is cleared too, the Fisher estimate is kept.  SAR: the running mean of the loss is forgotten too."""
     if model._tent is not None:
         with torch.inference_mode(False):
             model._tent.reset()
@@ -754,6 +868,57 @@ def deyo_step(model, batch):
         model.last_tta = dict(loss=loss, n_selected=info["counts"][0], n_reliable=info["counts"][1], entropy=info["H"],
                               plpd=info["plpd"], weight=info["w"], reliable=info["rel"], selected=info["sel"], y_hat_m=out_m,
                               probs=probs, y_hat_shuffled=zs, perm=perm)
+        return model._score_test(probs, y)
+
+
+def sar_reset_value(hp):
+    """tta_sar_reset resolved: None -> 0.2 ln K / ln 1000 (the published ImageNet constant at the same fraction of the maximal
+    entropy: this project's rule, not the paper's), False -> 0.0 (recovery disabled), a number -> itself."""
+    c = hp.tta_sar_reset
+    if c is False:
+        return 0.0
+    return 0.2 * math.log(hp.num_classes) / math.log(1000.0) if c is None else float(c)
+
+
+SAR_EMA_MOMENTUM = 0.9   # of the running mean of the second pass's loss: the published value
+
+
+def sar_step(model, batch):
+    """SAR (Niu et al., ICLR 2023) on one test batch, two adapting passes on the same inputs: (1) TENT's forward and
+    input-gradient-only backward with the loss (1/n1) sum of H_r over the rows with H_r < tta_e_margin, unweighted; (2) the ascent
+    step over A: saved <- A, A <- A + tta_sar_rho g / (|g| + 1e-12), |g| over the whole of A (stil_sar_perturb reads A and g from
+    the slabs; between the passes only A changes, the norm affines are read from the slab by their kernels and the conv / Linear
+    layouts that refresh_layouts rebuilds hold none of them, so no cached form of A survives); (3) the second pass at the perturbed
+    A, BatchNorm again by the batch's statistics (under tta_bn_prior), with the loss (1/n2) sum of H2_r over the rows the first pass
+    kept AND with H2_r < tta_e_margin; (4) A <- saved, a copy; (5) one Adam step over A on the second pass's gradients if and only if
+    n2 > 0; (6) with n2 > 0 the running mean of the second loss: ema <- L2, or 0.9 ema + 0.1 L2 when one is held; (7) unless
+    tta_sar_reset is False: when a running mean is held and lies below tta_sar_reset, A <- its source values, moments and step counts
+    cleared, the running mean forgotten -- after the Adam step, which it thereby discards, as in the published code.  n1, n2, the gate,
+    the running mean and the recovery decision stay on the device: the step reads nothing back.  Writes what tent_step writes and the
+    running mean.  The scores are softmax(out_m) of the FIRST pass, before any change.
+    last_tta: loss (L2), loss_first, n_selected (n2), n_first (n1), n_reliable (rows with H2 < margin), grad_norm (|g| of the first
+    pass, double), ema, ema_valid, recovered (after the step), entropy, entropy_second, selected_first, selected, y_hat_m, probs, all
+    on the device."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+        c = sar_reset_value(hp)
+        xs = _inputs(model, x)
+        out_m, loss1, probs, i1 = adapting_pass(model, xs, st, lambda z: sar_entropy(z, e0))
+        st.sel1 = i1["sel"]
+        st.perturb(hp.tta_sar_rho)
+        _, loss2, _, i2 = adapting_pass(model, xs, st, lambda z: sar_entropy(
+            z, e0, st.sel1, st.active, st.gate, st.ema, st.ema_valid, SAR_EMA_MOMENTUM, c, st.recover))
+        st.restore()
+        st.adam_step(hp.tta_lr, mask=st.gate)
+        if c > 0.0:
+            st.recover_if_flagged()
+        model.last_tta = dict(loss=loss2, loss_first=loss1, n_selected=i2["counts"][0], n_first=i1["counts"][0],
+                              n_reliable=i2["counts"][1], grad_norm=st.norm[0].clone(), ema=st.ema[0].clone(),
+                              ema_valid=st.ema_valid[0].clone(), recovered=st.recover[0].clone(), entropy=i1["H"],
+                              entropy_second=i2["H"], selected_first=i1["sel"], selected=i2["sel"], y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
 
 
