@@ -1,5 +1,5 @@
-"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h, include/stil_tta.h, include/stil_eata.h,
-include/stil_bnprior.h, include/stil_infomax.h, include/stil_margent.h, include/stil_deyo.h and include/stil_sar.h at import time.
+"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h and the test-time adaptation headers (TTA_HEADERS) at
+import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -14,13 +14,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "stil_hip.h")
-TTA_HEADER = os.path.join(_ROOT, "include", "stil_tta.h")   # test-time adaptation (kept out of stil_hip.h's ledger)
-EATA_HEADER = os.path.join(_ROOT, "include", "stil_eata.h")  # EATA on top of TENT (a ledger of its own)
-BNPRIOR_HEADER = os.path.join(_ROOT, "include", "stil_bnprior.h")  # test-time BatchNorm with a source prior (a ledger of its own)
-INFOMAX_HEADER = os.path.join(_ROOT, "include", "stil_infomax.h")  # SHOT's information-maximisation loss (a ledger of its own)
-MARGENT_HEADER = os.path.join(_ROOT, "include", "stil_margent.h")  # MEMO's marginal entropy over augmented views (a ledger of its own)
-DEYO_HEADER = os.path.join(_ROOT, "include", "stil_deyo.h")  # DeYO: the patch-shuffled view and the PLPD selection (a ledger of its own)
-SAR_HEADER = os.path.join(_ROOT, "include", "stil_sar.h")  # SAR: the two-pass row loss, the ascent step and the model recovery (a ledger of its own)
+# test-time adaptation, one header per method, kept out of stil_hip.h's ledger: tests/test_tta_abi_ledger_cpu.py holds theirs
+TTA_HEADERS = tuple(os.path.join(_ROOT, "include", f"stil_{n}.h") for n in ("tta", "eata", "bnprior", "infomax", "margent", "deyo", "sar"))
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -93,13 +88,8 @@ class _Lib:
                                f"(or `make -C {CSRC}`) first; there is no fallback path")
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
-        self.protos.update(parse_header(TTA_HEADER))
-        self.protos.update(parse_header(EATA_HEADER))
-        self.protos.update(parse_header(BNPRIOR_HEADER))
-        self.protos.update(parse_header(INFOMAX_HEADER))
-        self.protos.update(parse_header(MARGENT_HEADER))
-        self.protos.update(parse_header(DEYO_HEADER))
-        self.protos.update(parse_header(SAR_HEADER))
+        for header in TTA_HEADERS:
+            self.protos.update(parse_header(header))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks
             fn.restype = restype

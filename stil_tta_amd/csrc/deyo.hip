@@ -16,9 +16,10 @@
 //   active_out[t] = active[t] and n > 0                        (the gate of the Adam step: n never leaves the device)
 //   dZ_rk = sel_r w_r (-p_rk (log p_rk + H_r)) grad_scale / n  (0 when n == 0)
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
-// partials; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (which reads the double lse, H and
-// w of the first back).  The reduce and dZ kernels form the loss and f = w grad_scale / n as eata.hip's do, so that with
-// a_ent = 1, a_plpd = 0 the results are stil_eata_rows's (m invalid) bit for bit.
+// partials; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (tta_sel_dz_kernel of
+// csrc/tta.hip, which reads the double lse, H and w of the first back).  The loss and f = w grad_scale / n come from the code
+// eata.hip uses (tta_sel_sums, tta_sel_dz_kernel), so that with a_ent = 1, a_plpd = 0 the results are stil_eata_rows's
+// (m invalid) bit for bit.
 #include <limits.h>
 
 template <int VEC>
@@ -140,46 +141,16 @@ __global__ __launch_bounds__(256) void deyo_reduce_kernel(int rows, const float*
                                                            float* __restrict__ loss, const unsigned char* __restrict__ active,
                                                            unsigned char* __restrict__ active_out, int n_tensors) {
   __shared__ double redd[16];
-  double nd = 0.0, nr = 0.0, ls = 0.0;
-  for (int i = threadIdx.x; i < rows; i += 256) {
-    if (sel[i]) {
-      nd += 1.0;
-      ls += (double)w[i] * (double)H[i];
-    }
-    if (rel[i]) nr += 1.0;
-  }
-  nd = block_sum_d(nd, redd);  // integers below 2^53: exact
-  nr = block_sum_d(nr, redd);
-  ls = block_sum_d(ls, redd);
-  const int n = (int)nd;
+  const TtaSelSums sums = tta_sel_sums(rows, H, w, rel, sel, redd);
+  const int n = (int)sums.n;
   if (threadIdx.x == 0) {
     counts[0] = n;
-    counts[1] = (int)nr;
+    counts[1] = (int)sums.n_rel;
     counts[2] = 0;
     counts[3] = 0;
-    loss[0] = n > 0 ? (float)(ls / nd) : 0.f;
+    loss[0] = n > 0 ? (float)(sums.wh / sums.n) : 0.f;
   }
-  for (int t = threadIdx.x; t < n_tensors; t += 256) active_out[t] = (unsigned char)(active[t] && n > 0);
-}
-
-__global__ __launch_bounds__(256) void deyo_dz_kernel(const float* __restrict__ Z, int ld, int K, double gscale,
-                                                       const double* __restrict__ lse, const double* __restrict__ Hd,
-                                                       const double* __restrict__ Wd, const unsigned char* __restrict__ sel,
-                                                       const int* __restrict__ counts, float* __restrict__ dZ, int ldd) {
-  const int r = blockIdx.x;
-  const int n = counts[0];
-  float* dr = dZ + (long)r * ldd;
-  if (n <= 0 || !sel[r]) {  // uniform across the block
-    for (int k = threadIdx.x; k < K; k += 256) dr[k] = 0.f;
-    return;
-  }
-  const float* zr = Z + (long)r * ld;
-  const double L = lse[r], h = Hd[r];
-  const double f = Wd[r] * gscale / (double)n;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const double lp = (double)zr[k] - L;
-    dr[k] = (float)(-exp(lp) * (lp + h) * f);
-  }
+  tta_gate(active, active_out, n_tensors, n);
 }
 
 extern "C" int stil_deyo_rows(const float* Z, int ld, const float* Zs, int lds, int rows, int K, float ent_margin,
@@ -199,8 +170,8 @@ extern "C" int stil_deyo_rows(const float* Z, int ld, const float* Zs, int lds, 
   hipLaunchKernelGGL(deyo_reduce_kernel, dim3(1), dim3(256), 0, s, rows, (const float*)H, (const float*)w, (const unsigned char*)rel,
                      (const unsigned char*)sel, counts, loss, active, active_out, n_tensors);
   STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(deyo_dz_kernel, dim3(rows), dim3(256), 0, s, Z, ld, K, (double)grad_scale, (const double*)lse,
-                     (const double*)Hd, (const double*)Wd, (const unsigned char*)sel, (const int*)counts, dZ, ldd);
+  hipLaunchKernelGGL(tta_sel_dz_kernel<TtaWeightStored>, dim3(rows), dim3(256), 0, s, Z, ld, K, TtaWeightStored{Wd}, (double)grad_scale,
+                     (const double*)lse, (const double*)Hd, (const unsigned char*)sel, (const int*)counts, dZ, ldd);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

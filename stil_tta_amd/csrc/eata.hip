@@ -10,9 +10,10 @@
 //   active_out[t] = active[t] and n > 0                        (the gate of the Adam step: n never leaves the device)
 //   dZ_rk = sel_r w_r (-p_rk (log p_rk + H_r)) grad_scale / n  (0 when n == 0)
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
-// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (which reads the double lse and H of the first back).
-// The two slab kernels visit only the 1024-float chunks of A listed in `achunks` (checked against chunk2tensor / active as
-// stil_adam_step reads them); Fisher estimate and source values are compact: chunk j of them belongs to slab chunk achunks[j].
+// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (tta_sel_dz_kernel of csrc/tta.hip, which
+// reads the double lse and H of the first back).
+// The two slab kernels visit only the 1024-float chunks of A listed in `achunks` (tta_chunk_live of csrc/tta.hip: checked
+// against chunk2tensor / active as stil_adam_step reads them); Fisher estimate and source values are compact: chunk j of them belongs to slab chunk achunks[j].
 
 __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict__ Z, int ld, int K, double e0, double dm,
                                                          const float* __restrict__ m, const int* __restrict__ m_valid,
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict_
   }
 }
 
-// grid = cdiv(K, 256): every block counts n itself (rows bytes), block 0 writes the scalars and the gate
+// grid = cdiv(K, 256): every block forms the sums itself (rows bytes), block 0 writes the scalars and the gate
 __global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restrict__ p, int ldp, int rows, int K,
                                                            const float* __restrict__ H, const float* __restrict__ w,
                                                            const unsigned char* __restrict__ rel,
@@ -69,16 +70,8 @@ __global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restric
                                                            const unsigned char* __restrict__ active,
                                                            unsigned char* __restrict__ active_out, int n_tensors) {
   __shared__ double redd[16];
-  double nd = 0.0, nr = 0.0, ls = 0.0;
-  for (int i = threadIdx.x; i < rows; i += 256) {
-    if (sel[i]) {
-      nd += 1.0;
-      ls += (double)w[i] * (double)H[i];
-    }
-    if (rel[i]) nr += 1.0;
-  }
-  nd = block_sum_d(nd, redd);  // integers below 2^53: exact
-  const int n = (int)nd;
+  const TtaSelSums sums = tta_sel_sums(rows, H, w, rel, sel, redd);
+  const int n = (int)sums.n;
   const int valid = counts[2];
   if (n > 0) {
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -86,40 +79,18 @@ __global__ __launch_bounds__(256) void eata_reduce_kernel(const float* __restric
       double s = 0.0;
       for (int r = 0; r < rows; ++r)
         if (sel[r]) s += (double)p[(long)r * ldp + k];  // fixed order
-      s /= nd;
+      s /= sums.n;
       m[k] = (float)(valid ? mu * (double)m[k] + (1.0 - mu) * s : s);
     }
   }
   if (blockIdx.x != 0) return;
-  nr = block_sum_d(nr, redd);
-  ls = block_sum_d(ls, redd);
   if (threadIdx.x == 0) {
     counts[0] = n;
-    counts[1] = (int)nr;
-    loss[0] = n > 0 ? (float)(ls / nd) : 0.f;
+    counts[1] = (int)sums.n_rel;
+    loss[0] = n > 0 ? (float)(sums.wh / sums.n) : 0.f;
     if (n > 0) m_valid[0] = 1;
   }
-  for (int t = threadIdx.x; t < n_tensors; t += 256) active_out[t] = (unsigned char)(active[t] && n > 0);
-}
-
-__global__ __launch_bounds__(256) void eata_dz_kernel(const float* __restrict__ Z, int ld, int K, double e0, double gscale,
-                                                       const double* __restrict__ lse, const double* __restrict__ Hd,
-                                                       const unsigned char* __restrict__ sel, const int* __restrict__ counts,
-                                                       float* __restrict__ dZ, int ldd) {
-  const int r = blockIdx.x;
-  const int n = counts[0];
-  float* dr = dZ + (long)r * ldd;
-  if (n <= 0 || !sel[r]) {  // uniform across the block
-    for (int k = threadIdx.x; k < K; k += 256) dr[k] = 0.f;
-    return;
-  }
-  const float* zr = Z + (long)r * ld;
-  const double L = lse[r], h = Hd[r];  // the rows kernel's double lse and H of this row
-  const double f = exp(e0 - h) * gscale / (double)n;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const double lp = (double)zr[k] - L;
-    dr[k] = (float)(-exp(lp) * (lp + h) * f);
-  }
+  tta_gate(active, active_out, n_tensors, n);
 }
 
 extern "C" int stil_eata_rows(const float* Z, int ld, int rows, int K, float e_margin, float d_margin, float momentum,
@@ -139,20 +110,13 @@ extern "C" int stil_eata_rows(const float* Z, int ld, int rows, int K, float e_m
                      (const float*)w, (const unsigned char*)rel, (const unsigned char*)sel, (double)momentum, m, m_valid, counts,
                      loss, active, active_out, n_tensors);
   STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(eata_dz_kernel, dim3(rows), dim3(256), 0, s, Z, ld, K, (double)e_margin, (double)grad_scale,
+  hipLaunchKernelGGL(tta_sel_dz_kernel<TtaWeightMargin>, dim3(rows), dim3(256), 0, s, Z, ld, K, TtaWeightMargin{(double)e_margin}, (double)grad_scale,
                      (const double*)lse, (const double*)Hd, (const unsigned char*)sel, (const int*)counts, dZ, ldd);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
 
 // ---- the Fisher anchor and the Fisher accumulation: one block per listed chunk
-__device__ __forceinline__ bool eata_chunk_live(int ch, long nchunks, const int* __restrict__ chunk2tensor,
-                                                const unsigned char* __restrict__ active, int n_tensors) {
-  if (ch < 0 || ch >= nchunks) return false;
-  const int t = chunk2tensor[ch];
-  return t >= 0 && t < n_tensors && active[t];
-}
-
 __global__ __launch_bounds__(256) void eata_anchor_kernel(const float* __restrict__ params, const float* __restrict__ theta0,
                                                            const float* __restrict__ fisher, float* __restrict__ grads,
                                                            const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
@@ -160,7 +124,7 @@ __global__ __launch_bounds__(256) void eata_anchor_kernel(const float* __restric
                                                            double alpha, double* __restrict__ partial) {
   __shared__ double redd[16];
   const int j = blockIdx.x, ch = achunks[j];
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
     if (threadIdx.x == 0) partial[j] = 0.0;
     return;
   }
@@ -197,7 +161,7 @@ __global__ __launch_bounds__(256) void eata_fisher_kernel(float* __restrict__ fi
                                                            const unsigned char* __restrict__ active, int n_tensors, long nchunks,
                                                            double scale) {
   const int j = blockIdx.x, ch = achunks[j];
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
   const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
   const float4 gg = reinterpret_cast<const float4*>(grads)[i];
   float4 ff = reinterpret_cast<float4*>(fisher)[ic];
@@ -212,7 +176,7 @@ extern "C" int stil_eata_anchor(const float* params, const float* theta0, const 
                                 int n_achunks, const int* chunk2tensor, const unsigned char* active, int n_tensors, long n,
                                 float alpha, double* partial, float* R, void* stream) {
   STIL_REQUIRE(params && theta0 && fisher && grads && achunks && chunk2tensor && active && partial && R, "stil_eata_anchor: null pointer");
-  STIL_REQUIRE(n >= 0 && n % 1024 == 0 && n_achunks >= 0 && n_tensors >= 0, "stil_eata_anchor: n=%ld must be a multiple of 1024, n_achunks=%d", n, n_achunks);
+  TTA_SLAB_REQUIRE("stil_eata_anchor");
   STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0) && ((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0),
                "stil_eata_anchor: slabs must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
@@ -229,7 +193,7 @@ extern "C" int stil_eata_anchor(const float* params, const float* theta0, const 
 extern "C" int stil_eata_fisher_accum(float* fisher, const float* grads, const int* achunks, int n_achunks, const int* chunk2tensor,
                                       const unsigned char* active, int n_tensors, long n, float scale, void* stream) {
   STIL_REQUIRE(fisher && grads && achunks && chunk2tensor && active, "stil_eata_fisher_accum: null pointer");
-  STIL_REQUIRE(n >= 0 && n % 1024 == 0 && n_achunks >= 0 && n_tensors >= 0, "stil_eata_fisher_accum: n=%ld must be a multiple of 1024, n_achunks=%d", n, n_achunks);
+  TTA_SLAB_REQUIRE("stil_eata_fisher_accum");
   STIL_REQUIRE(((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0), "stil_eata_fisher_accum: slabs must be 16-byte aligned");
   if (n_achunks == 0) return STIL_OK;
   hipLaunchKernelGGL(eata_fisher_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, fisher, grads, achunks, chunk2tensor,

@@ -8,9 +8,9 @@
 //   dZ_rk = sel_r (-p_rk (log p_rk + H_r)) grad_scale / n      (0 when n == 0)
 //   second pass: ema <- L | mu ema + (1 - mu) L when n > 0 ; recover = reset > 0 and ema held and ema < reset
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
-// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (which
-// reads the double lse and H of the first back).
-// The slab kernels visit only the 1024-float chunks of A listed in `achunks` (eata_chunk_live of csrc/eata.hip: checked
+// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ
+// (tta_sel_dz_kernel of csrc/tta.hip with weight 1, which reads the double lse and H of the first back).
+// The slab kernels visit only the 1024-float chunks of A listed in `achunks` (tta_chunk_live of csrc/tta.hip: checked
 // against chunk2tensor / active as stil_adam_step reads them); saved values, the perturbation and the source values are
 // compact: chunk j of them belongs to slab chunk achunks[j].  What one block hands to another crosses a launch boundary.
 
@@ -76,27 +76,7 @@ __global__ __launch_bounds__(256) void sar_reduce_kernel(int rows, double e0, co
       recover[0] = (reset > 0.0 && valid && (double)e < reset) ? 1 : 0;  // on the float the state holds
     }
   }
-  for (int t = threadIdx.x; t < n_tensors; t += 256) active_out[t] = (unsigned char)(active[t] && n > 0);
-}
-
-__global__ __launch_bounds__(256) void sar_dz_kernel(const float* __restrict__ Z, int ld, int K, double gscale,
-                                                      const double* __restrict__ lse, const double* __restrict__ Hd,
-                                                      const unsigned char* __restrict__ sel, const int* __restrict__ counts,
-                                                      float* __restrict__ dZ, int ldd) {
-  const int r = blockIdx.x;
-  const int n = counts[0];
-  float* dr = dZ + (long)r * ldd;
-  if (n <= 0 || !sel[r]) {  // uniform across the block
-    for (int k = threadIdx.x; k < K; k += 256) dr[k] = 0.f;
-    return;
-  }
-  const float* zr = Z + (long)r * ld;
-  const double L = lse[r], h = Hd[r];  // the rows kernel's double lse and H of this row
-  const double f = gscale / (double)n;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const double lp = (double)zr[k] - L;
-    dr[k] = (float)(-exp(lp) * (lp + h) * f);
-  }
+  tta_gate(active, active_out, n_tensors, n);
 }
 
 extern "C" int stil_sar_rows(const float* Z, int ld, int rows, int K, float margin, float grad_scale, const unsigned char* prior_sel,
@@ -116,8 +96,8 @@ extern "C" int stil_sar_rows(const float* Z, int ld, int rows, int K, float marg
                      (const unsigned char*)sel, counts, loss, active, active_out, n_tensors, ema, ema_valid, (double)momentum,
                      (double)reset, recover);
   STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sar_dz_kernel, dim3(rows), dim3(256), 0, s, Z, ld, K, (double)grad_scale, (const double*)lse, (const double*)Hd,
-                     (const unsigned char*)sel, (const int*)counts, dZ, ldd);
+  hipLaunchKernelGGL(tta_sel_dz_kernel<TtaWeightOne>, dim3(rows), dim3(256), 0, s, Z, ld, K, TtaWeightOne{}, (double)grad_scale,
+                     (const double*)lse, (const double*)Hd, (const unsigned char*)sel, (const int*)counts, dZ, ldd);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(256) void sar_sqnorm_kernel(const float* __restrict
                                                           double* __restrict__ partial) {
   __shared__ double redd[16];
   const int j = blockIdx.x, ch = achunks[j];
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
     if (threadIdx.x == 0) partial[j] = 0.0;
     return;
   }
@@ -154,7 +134,7 @@ __global__ __launch_bounds__(256) void sar_perturb_kernel(float* __restrict__ pa
   const double nrm = sqrt(s);
   const int j = blockIdx.x, ch = achunks[j];
   if (j == 0 && threadIdx.x == 0) norm[0] = nrm;
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
   const double f = rho / (nrm + 1e-12);
   const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
   const float4 g = reinterpret_cast<const float4*>(grads)[i];
@@ -181,7 +161,7 @@ __global__ __launch_bounds__(256) void sar_restore_kernel(float* __restrict__ pa
                                                            const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
                                                            const unsigned char* __restrict__ active, int n_tensors, long nchunks) {
   const int j = blockIdx.x, ch = achunks[j];
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
   reinterpret_cast<float4*>(params)[(long)ch * 256 + threadIdx.x] = reinterpret_cast<const float4*>(saved)[(long)j * 256 + threadIdx.x];
 }
 
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(256) void sar_recover_kernel(float* __restrict__ pa
     return;
   }
   const int ch = achunks[j];
-  if (!eata_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
   const long i = (long)ch * 256 + threadIdx.x;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   reinterpret_cast<float4*>(params)[i] = reinterpret_cast<const float4*>(theta0)[(long)j * 256 + threadIdx.x];
@@ -209,14 +189,11 @@ __global__ __launch_bounds__(256) void sar_recover_kernel(float* __restrict__ pa
   reinterpret_cast<float4*>(exp_avg_sq)[i] = zero;
 }
 
-#define SAR_SLAB_REQUIRE(name)                                                                                          \
-  STIL_REQUIRE(n >= 0 && n % 1024 == 0 && n_achunks >= 0 && n_tensors >= 0, name ": n=%ld must be a multiple of 1024, n_achunks=%d", n, n_achunks)
-
 extern "C" int stil_sar_perturb(float* params, const float* grads, float* saved, float* e, const int* achunks, int n_achunks,
                                 const int* chunk2tensor, const unsigned char* active, int n_tensors, long n, float rho, double* partial,
                                 double* norm, void* stream) {
   STIL_REQUIRE(params && grads && saved && e && achunks && chunk2tensor && active && partial && norm, "stil_sar_perturb: null pointer");
-  SAR_SLAB_REQUIRE("stil_sar_perturb");
+  TTA_SLAB_REQUIRE("stil_sar_perturb");
   STIL_REQUIRE(rho >= 0.f && rho <= 3.0e38f, "stil_sar_perturb: rho=%g must be a finite number >= 0", (double)rho);
   STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)grads % 16 == 0) && ((uintptr_t)saved % 16 == 0) && ((uintptr_t)e % 16 == 0),
                "stil_sar_perturb: slabs must be 16-byte aligned");
@@ -237,7 +214,7 @@ extern "C" int stil_sar_perturb(float* params, const float* grads, float* saved,
 extern "C" int stil_sar_restore(float* params, const float* saved, const int* achunks, int n_achunks, const int* chunk2tensor,
                                 const unsigned char* active, int n_tensors, long n, void* stream) {
   STIL_REQUIRE(params && saved && achunks && chunk2tensor && active, "stil_sar_restore: null pointer");
-  SAR_SLAB_REQUIRE("stil_sar_restore");
+  TTA_SLAB_REQUIRE("stil_sar_restore");
   STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)saved % 16 == 0), "stil_sar_restore: slabs must be 16-byte aligned");
   if (n_achunks == 0) return STIL_OK;
   hipLaunchKernelGGL(sar_restore_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, params, saved, achunks, chunk2tensor, active,
@@ -251,7 +228,7 @@ extern "C" int stil_sar_recover(float* params, const float* theta0, float* exp_a
                                 const int* recover, int* ema_valid, void* stream) {
   STIL_REQUIRE(params && theta0 && exp_avg && exp_avg_sq && steps && achunks && chunk2tensor && active && recover && ema_valid,
                "stil_sar_recover: null pointer");
-  SAR_SLAB_REQUIRE("stil_sar_recover");
+  TTA_SLAB_REQUIRE("stil_sar_recover");
   STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0) && ((uintptr_t)exp_avg % 16 == 0) && ((uintptr_t)exp_avg_sq % 16 == 0),
                "stil_sar_recover: slabs must be 16-byte aligned");
   hipLaunchKernelGGL(sar_recover_kernel, dim3(n_achunks + 1), dim3(256), 0, (hipStream_t)stream, params, theta0, exp_avg, exp_avg_sq, steps,
@@ -259,4 +236,3 @@ extern "C" int stil_sar_recover(float* params, const float* theta0, float* exp_a
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
-#undef SAR_SLAB_REQUIRE

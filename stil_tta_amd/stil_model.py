@@ -661,8 +661,7 @@ class STiLModel(_Base):
         With "sar" (tta.sar_step) the batch runs two adapting passes, the second at A + tta_sar_rho g / |g|, and A recovers its
         source values when the running mean of the loss falls below tta_sar_reset; the scores are the first pass's."""
         if self._tta_on():
-            return {"tent": tta.tent_step, "eata": tta.eata_step, "bn_adapt": tta.bn_adapt_step, "shot_im": tta.shot_im_step,
-                    "marginal_entropy": tta.marginal_entropy_step, "deyo": tta.deyo_step, "sar": tta.sar_step}[self.hp.tta_method](self, batch)
+            return tta.STEPS[self.hp.tta_method](self, batch)
         with torch.no_grad():
             x, y = batch
             self.setup_device()

@@ -35,9 +35,26 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-METHODS = (None, "tent", "eata", "bn_adapt", "shot_im", "marginal_entropy", "deyo", "sar")
 PARAMS = ("bn", "norm")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
+
+
+def _number(hp, key, lo=None, strict=False, also=()):
+    """hp.<key> must be one of `also` (None, False) or a finite number (no bool), not below `lo` when one is given (`strict`:
+    above it)"""
+    v = getattr(hp, key)
+    if any(v is a for a in also):
+        return
+    ok = not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+    if not ok or (lo is not None and (v <= lo if strict else v < lo)):
+        bound = "" if lo is None else f" {'>' if strict else '>='} {lo}"
+        raise ValueError(f"{key} must be {', '.join(map(str, also)) + ' or ' if also else ''}a finite number{bound}, not {v!r}")
+
+
+def _int_from(hp, key, lo):
+    v = getattr(hp, key)
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+        raise ValueError(f"{key} must be an int >= {lo}, not {v!r}")
 
 
 def check_hparams(hp):
@@ -45,40 +62,23 @@ def check_hparams(hp):
         raise ValueError(f"Unknown tta_method {hp.tta_method!r}: valid are {METHODS}")
     if hp.tta_params not in PARAMS:
         raise ValueError(f"Unknown tta_params {hp.tta_params!r}: valid are {PARAMS}")
-    N = hp.tta_bn_prior
-    if N is not None and (isinstance(N, bool) or not isinstance(N, (int, float)) or not math.isfinite(N) or N < 0):
-        raise ValueError(f"tta_bn_prior must be None or a finite number >= 0, not {N!r}")
-    w, e = hp.tta_div_weight, hp.tta_div_eps
-    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
-        raise ValueError(f"tta_div_weight must be a finite number >= 0, not {w!r}")
-    if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or e <= 0:
-        raise ValueError(f"tta_div_eps must be a finite number > 0, not {e!r}")
-    V, seed = hp.tta_views, hp.tta_view_seed
-    if isinstance(V, bool) or not isinstance(V, int) or V < 1:
-        raise ValueError(f"tta_views must be an int >= 1, not {V!r}")
+    _number(hp, "tta_bn_prior", 0, also=(None,))
+    _number(hp, "tta_div_weight", 0)
+    _number(hp, "tta_div_eps", 0, strict=True)
+    _int_from(hp, "tta_views", 1)
     if not isinstance(hp.tta_view_policy, str) or hp.tta_view_policy not in VIEW_POLICIES:
         raise ValueError(f"Unknown tta_view_policy {hp.tta_view_policy!r}: valid are {VIEW_POLICIES}")
-    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:   # the generator takes no negative seed
-        raise ValueError(f"tta_view_seed must be an int >= 0, not {seed!r}")
+    _int_from(hp, "tta_view_seed", 0)   # the generator takes no negative seed
     g = hp.tta_patch_grid
     if isinstance(g, bool) or not isinstance(g, int) or g < 1 or hp.img_size % g != 0:
         raise ValueError(f"tta_patch_grid must be an int >= 1 that divides img_size = {hp.img_size}, not {g!r}")
-    for name in ("tta_ent_margin", "tta_plpd_margin"):
-        v = getattr(hp, name)
-        if (v is not None or name == "tta_plpd_margin") and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v)):
-            raise ValueError(f"{name} must be {'None or ' if name == 'tta_ent_margin' else ''}a finite number, not {v!r}")
-    for name in ("tta_reweight_ent", "tta_reweight_plpd"):
-        v = getattr(hp, name)
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
-    seed = hp.tta_shuffle_seed
-    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
-        raise ValueError(f"tta_shuffle_seed must be an int >= 0, not {seed!r}")
-    rho, c = hp.tta_sar_rho, hp.tta_sar_reset
-    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not math.isfinite(rho) or rho < 0:
-        raise ValueError(f"tta_sar_rho must be a finite number >= 0, not {rho!r}")
-    if c is not None and c is not False and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0):
-        raise ValueError(f"tta_sar_reset must be None, False or a finite number > 0, not {c!r}")
+    _number(hp, "tta_ent_margin", also=(None,))
+    _number(hp, "tta_plpd_margin")
+    _number(hp, "tta_reweight_ent", 0)
+    _number(hp, "tta_reweight_plpd", 0)
+    _int_from(hp, "tta_shuffle_seed", 0)
+    _number(hp, "tta_sar_rho", 0)
+    _number(hp, "tta_sar_reset", 0, strict=True, also=(None, False))   # True is refused: False alone switches recovery off
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -102,165 +102,136 @@ def param_names(model) -> List[str]:
 
 
 # ---------------------------------------------------------------------------------------------- losses
-class EntropyFn(torch.autograd.Function):
-    """TENT's loss (Wang et al., ICLR 2021): mean over rows of H(softmax(z)), H(p) = -sum_k p_k log p_k, for test-time
-    adaptation in STiLModel.test_step (STiLModel.py:523-524).  -> (loss, probabilities); the probabilities (no gradient)
-    are the scores the step reports, so no separate softmax launch runs.  One launch forms lse, p, the row entropies and
-    dZ / rows (stil_entropy_rows); backward scales dZ by the incoming gradient."""
+class _RowLossFn(torch.autograd.Function):
+    """The one autograd node of the six losses below: launch(z) -> (loss, probabilities or None, dZ) makes the loss's single
+    library call, which forms dZ in the same launch sequence; the probabilities carry no gradient and backward scales dZ by the
+    incoming gradient."""
 
     @staticmethod
-    def forward(ctx, z):
-        _chk(z)
-        R, K = z.shape
-        dev = z.device
-        lse = torch.empty((R,), dtype=torch.float64, device=dev)
-        p = torch.empty_like(z)
-        h = torch.empty((R,), dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        lib().entropy_rows(_p(z), K, R, K, 1.0 / R, _p(lse), _p(p), K, _p(h), _p(dz), K, _p(loss), _stream())
+    def forward(ctx, z, launch):
+        loss, p, dz = launch(z)
         ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
+        if p is not None:
+            ctx.mark_non_differentiable(p)
         return loss, p
 
     @staticmethod
     def backward(ctx, g, _gp=None):
         (dz,) = ctx.saved_tensors
-        return _scale_by(dz, g)
+        return _scale_by(dz, g), None
+
+
+def _empty(z, n, dtype, count=None):
+    """-> one uninitialised [n] tensor of `dtype` on z's device, or a generator of `count` of them"""
+    if count is None:
+        return torch.empty((n,), dtype=dtype, device=z.device)
+    return (torch.empty((n,), dtype=dtype, device=z.device) for _ in range(count))
 
 
 def entropy(z):
-    """-> (mean row entropy of softmax(z) [autograd], softmax(z) [no grad], {})"""
-    return EntropyFn.apply(z.contiguous()) + ({},)
+    """TENT's loss (Wang et al., ICLR 2021): mean over rows of H(softmax(z)), H(p) = -sum_k p_k log p_k, for test-time
+    adaptation in STiLModel.test_step (STiLModel.py:523-524).  The probabilities are the scores the step reports, so no
+    separate softmax launch runs.  One launch forms lse, p, the row entropies and dZ / rows (stil_entropy_rows).
+    -> (mean row entropy of softmax(z) [autograd], softmax(z) [no grad], {})"""
+    def launch(z):
+        _chk(z)
+        R, K = z.shape
+        lse, h = _empty(z, R, torch.float64), _empty(z, R, torch.float32)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        lib().entropy_rows(_p(z), K, R, K, 1.0 / R, _p(lse), _p(p), K, _p(h), _p(dz), K, _p(loss), _stream())
+        return loss, p, dz
+
+    return _RowLossFn.apply(z.contiguous(), launch) + ({},)
 
 
-class EataEntropyFn(torch.autograd.Function):
-    """EATA's loss (Niu et al., ICML 2022) beside EntropyFn: (1/n) sum over the selected rows of w_r H_r, the selection
+def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=None):
+    """EATA's loss (Niu et al., ICML 2022) beside entropy: (1/n) sum over the selected rows of w_r H_r, the selection
     (reliable: H_r < e_margin; non-redundant: |cos(m, p_r)| < d_margin), the weights w_r = exp(e_margin - H_r), the update of
-    the running mean m and the gate of the Adam step, all in stil_eata_rows: n stays on the device.
-    -> (loss, probabilities, info); info = dict(H, cos, w, rel, sel, counts [n, n_reliable, m valid before, -], lse).
-    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient; w carries no gradient."""
+    the running mean m and the gate of the Adam step, all in stil_eata_rows: n stays on the device.  dZ is already divided by n
+    (zero when n == 0); w carries no gradient.
+    -> (EATA's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates m / m_valid / gate;
+    info = dict(H, cos, w, rel, sel, counts [n, n_reliable, m valid before, -], lse)."""
+    info = {}
 
-    @staticmethod
-    def forward(ctx, z, e_margin, d_margin, momentum, m, m_valid, active, gate, info):
+    def launch(z):
         _chk(z, m, m_valid, active, gate)
         R, K = z.shape
-        dev = z.device
-        lse, hd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
-        p = torch.empty_like(z)
-        h, c, w = (torch.empty((R,), dtype=torch.float32, device=dev) for _ in range(3))
-        rel, sel = (torch.empty((R,), dtype=torch.uint8, device=dev) for _ in range(2))
-        dz = torch.empty_like(z)
-        counts = torch.zeros((4,), dtype=torch.int32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lse, hd = _empty(z, R, torch.float64, 2)
+        h, c, w = _empty(z, R, torch.float32, 3)
+        rel, sel = _empty(z, R, torch.uint8, 2)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        counts = torch.zeros((4,), dtype=torch.int32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
         nt = 0 if active is None else active.numel()
         lib().eata_rows(_p(z), K, R, K, float(e_margin), float(d_margin), float(momentum), 1.0, _p(m), _p(m_valid), _p(lse), _p(hd), _p(p), K,
                         _p(h), _p(c), _p(w), _p(rel), _p(sel), _p(dz), K, _p(counts), _p(loss), _p(active), _p(gate), nt, _stream())
         info.update(H=h, cos=c, w=w, rel=rel, sel=sel, counts=counts, lse=lse)
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return loss, p
+        return loss, p, dz
 
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return (_scale_by(dz, g),) + (None,) * 8
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
-def eata_entropy(z, e_margin, d_margin, momentum, m, m_valid, active=None, gate=None):
-    """-> (EATA's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates m / m_valid / gate."""
-    info = {}
-    loss, p = EataEntropyFn.apply(z.contiguous(), e_margin, d_margin, momentum, m, m_valid, active, gate, info)
-    return loss, p, info
-
-
-class DeyoFn(torch.autograd.Function):
-    """DeYO's loss (Lee et al., ICLR 2024) beside EataEntropyFn: (1/n) sum over the selected rows of w_r H_r, with z the logits
+def deyo_entropy(z, zs, ent_margin, plpd_margin, e0, a_ent=1.0, a_plpd=1.0, active=None, gate=None):
+    """DeYO's loss (Lee et al., ICLR 2024) beside eata_entropy: (1/n) sum over the selected rows of w_r H_r, with z the logits
     of the batch and zs those of its patch-shuffled images (no gradient).  plpd_r = p_r[yhat_r] - softmax(zs_r)[yhat_r], yhat_r
     the first maximum of z_r; the selection (reliable: H_r < ent_margin; and plpd_r > plpd_margin), the weights w_r =
     a_ent exp(e0 - H_r) + a_plpd exp(plpd_r) and the gate of the Adam step, all in stil_deyo_rows: n stays on the device.
-    -> (loss, probabilities); info = dict(H, plpd, w, yhat, rel, sel, counts [n, n_reliable, 0, 0], lse).
-    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient; w carries no gradient."""
+    dZ is already divided by n (zero when n == 0); w carries no gradient.
+    -> (DeYO's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate;
+    info = dict(H, plpd, w, yhat, rel, sel, counts [n, n_reliable, 0, 0], lse)."""
+    info = {}
+    zs = zs.detach().contiguous()
 
-    @staticmethod
-    def forward(ctx, z, zs, ent_margin, plpd_margin, e0, a_ent, a_plpd, active, gate, info):
+    def launch(z):
         _chk(z, zs, active, gate)
         R, K = z.shape
         if tuple(zs.shape) != (R, K):
             raise ValueError(f"deyo_entropy: logits {tuple(z.shape)} against shuffled logits {tuple(zs.shape)}")
-        dev = z.device
-        lse, hd, wd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(3))
-        p = torch.empty_like(z)
-        h, d, w = (torch.empty((R,), dtype=torch.float32, device=dev) for _ in range(3))
-        yhat = torch.empty((R,), dtype=torch.int32, device=dev)
-        rel, sel = (torch.empty((R,), dtype=torch.uint8, device=dev) for _ in range(2))
-        dz = torch.empty_like(z)
-        counts = torch.empty((4,), dtype=torch.int32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lse, hd, wd = _empty(z, R, torch.float64, 3)
+        h, d, w = _empty(z, R, torch.float32, 3)
+        yhat = _empty(z, R, torch.int32)
+        rel, sel = _empty(z, R, torch.uint8, 2)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        counts = torch.empty((4,), dtype=torch.int32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
         nt = 0 if active is None else active.numel()
         lib().deyo_rows(_p(z), K, _p(zs), K, R, K, float(ent_margin), float(plpd_margin), float(e0), float(a_ent), float(a_plpd), 1.0,
                         _p(lse), _p(hd), _p(wd), _p(p), K, _p(h), _p(d), _p(w), _p(yhat), _p(rel), _p(sel), _p(dz), K, _p(counts),
                         _p(loss), _p(active), _p(gate), nt, _stream())
         info.update(H=h, plpd=d, w=w, yhat=yhat, rel=rel, sel=sel, counts=counts, lse=lse)
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return loss, p
+        return loss, p, dz
 
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return (_scale_by(dz, g),) + (None,) * 9
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
-def deyo_entropy(z, zs, ent_margin, plpd_margin, e0, a_ent=1.0, a_plpd=1.0, active=None, gate=None):
-    """-> (DeYO's weighted entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate."""
-    info = {}
-    loss, p = DeyoFn.apply(z.contiguous(), zs.detach().contiguous(), ent_margin, plpd_margin, e0, a_ent, a_plpd, active, gate, info)
-    return loss, p, info
-
-
-class SarEntropyFn(torch.autograd.Function):
-    """SAR's loss (Niu et al., ICLR 2023) beside EataEntropyFn: (1/n) sum over the selected rows of H_r, unweighted; a row is
+def sar_entropy(z, margin, prior=None, active=None, gate=None, ema=None, ema_valid=None, momentum=0.9, reset=0.0, recover=None):
+    """SAR's loss (Niu et al., ICLR 2023) beside eata_entropy: (1/n) sum over the selected rows of H_r, unweighted; a row is
     selected when H_r < margin and, in the second pass, the first pass selected it too (`prior`, its `sel`).  With `ema` (the
-    second pass) the running mean of the loss and the recovery flag are updated as well, all in stil_sar_rows: n, the gate of
-    the Adam step and the recovery decision stay on the device.
-    -> (loss, probabilities); info = dict(H, sel, counts [n, rows with H < margin, rows the prior admits, 0], lse).
-    Backward scales dZ (already divided by n; zero when n == 0) by the incoming gradient."""
+    second pass) the running mean of the loss (ema, ema_valid) and the recovery flag (reset <= 0: never raised) are updated as
+    well, all in stil_sar_rows: n, the gate of the Adam step and the recovery decision stay on the device.  dZ is already
+    divided by n (zero when n == 0).
+    -> (the mean entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate;
+    info = dict(H, sel, counts [n, rows with H < margin, rows the prior admits, 0], lse)."""
+    info = {}
 
-    @staticmethod
-    def forward(ctx, z, margin, prior, active, gate, ema, ema_valid, momentum, reset, recover, info):
+    def launch(z):
         _chk(z, prior, active, gate, ema, ema_valid, recover)
         R, K = z.shape
         if prior is not None and (prior.dtype != torch.uint8 or prior.numel() != R):
             raise ValueError(f"sar_entropy: a prior selection of {prior.numel()} {prior.dtype} entries for {R} rows")
-        dev = z.device
-        lse, hd = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
-        p = torch.empty_like(z)
-        h = torch.empty((R,), dtype=torch.float32, device=dev)
-        sel = torch.empty((R,), dtype=torch.uint8, device=dev)
-        dz = torch.empty_like(z)
-        counts = torch.empty((4,), dtype=torch.int32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lse, hd = _empty(z, R, torch.float64, 2)
+        h, sel = _empty(z, R, torch.float32), _empty(z, R, torch.uint8)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        counts = torch.empty((4,), dtype=torch.int32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
         nt = 0 if active is None else active.numel()
         lib().sar_rows(_p(z), K, R, K, float(margin), 1.0, _p(prior), _p(lse), _p(hd), _p(p), K, _p(h), _p(sel), _p(dz), K, _p(counts),
                        _p(loss), _p(active), _p(gate), nt, _p(ema), _p(ema_valid), float(momentum), float(reset), _p(recover), _stream())
         info.update(H=h, sel=sel, counts=counts, lse=lse)
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return loss, p
+        return loss, p, dz
 
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return (_scale_by(dz, g),) + (None,) * 10
-
-
-def sar_entropy(z, margin, prior=None, active=None, gate=None, ema=None, ema_valid=None, momentum=0.9, reset=0.0, recover=None):
-    """-> (the mean entropy of the selected rows [autograd], softmax(z) [no grad], info); updates gate, and with `ema` the
-    running mean of the loss (ema, ema_valid) and the recovery flag (reset <= 0: never raised)."""
-    info = {}
-    loss, p = SarEntropyFn.apply(z.contiguous(), margin, prior, active, gate, ema, ema_valid, momentum, reset, recover, info)
-    return loss, p, info
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
 def patch_shuffle(x, grid, perm):
@@ -289,86 +260,58 @@ def patch_shuffle(x, grid, perm):
     return out
 
 
-class InfoMaxFn(torch.autograd.Function):
-    """SHOT's information-maximisation loss (Liang et al., ICML 2020) beside EntropyFn: mean row entropy of softmax(z) plus
+def infomax(z, div_weight=1.0, eps=1e-5):
+    """SHOT's information-maximisation loss (Liang et al., ICML 2020) beside entropy: mean row entropy of softmax(z) plus
     div_weight x D, D = sum_k pbar_k log(pbar_k + eps) with pbar the batch mean of the rows' softmax (minus the entropy of the
     marginal: it penalises the batch that predicts one class everywhere).  stil_infomax_rows forms lse, p, the row entropies,
-    pbar, D and dZ / rows; the gradient couples the rows through pbar.  -> (loss, probabilities); info = dict(loss_entropy,
-    loss_diversity, marginal [K], H, lse), all on the device.  Backward scales dZ by the incoming gradient.  With
-    div_weight == 0 loss, probabilities and dZ are EntropyFn's bit for bit."""
+    pbar, D and dZ / rows; the gradient couples the rows through pbar.  With div_weight == 0 loss, probabilities and dZ are
+    entropy's bit for bit.
+    -> (mean row entropy + div_weight x D of softmax(z) [autograd], softmax(z) [no grad], info);
+    info = dict(loss_entropy, loss_diversity, marginal [K], H, lse), all on the device."""
+    info = {}
 
-    @staticmethod
-    def forward(ctx, z, div_weight, eps, info):
+    def launch(z):
         _chk(z)
         R, K = z.shape
-        dev = z.device
-        lse = torch.empty((R,), dtype=torch.float64, device=dev)
-        p = torch.empty_like(z)
-        h = torch.empty((R,), dtype=torch.float32, device=dev)
-        pbar = torch.empty((K,), dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z)
-        out = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((2 * K + R,), dtype=torch.float64, device=dev)
+        lse, h, pbar = _empty(z, R, torch.float64), _empty(z, R, torch.float32), _empty(z, K, torch.float32)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        out = _empty(z, 3, torch.float32)
+        ws = _empty(z, 2 * K + R, torch.float64)
         lib().infomax_rows(_p(z), K, R, K, 1.0 / R, float(div_weight), float(eps), _p(lse), _p(p), K, _p(h), _p(pbar), _p(dz), K,
                            _p(out), _p(ws), _stream())
         info.update(loss_entropy=out[1], loss_diversity=out[2], marginal=pbar, H=h, lse=lse)
-        ctx.save_for_backward(dz)
-        ctx.mark_non_differentiable(p)
-        return out[0], p
+        return out[0], p, dz
 
-    @staticmethod
-    def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return _scale_by(dz, g), None, None, None
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
-def infomax(z, div_weight=1.0, eps=1e-5):
-    """-> (mean row entropy + div_weight x D of softmax(z) [autograd], softmax(z) [no grad], info)"""
-    info = {}
-    loss, p = InfoMaxFn.apply(z.contiguous(), div_weight, eps, info)
-    return loss, p, info
-
-
-class MarginalEntropyFn(torch.autograd.Function):
-    """MEMO's loss (Zhang, Levine, Finn, NeurIPS 2022) beside EntropyFn: z holds `views` consecutive rows per sample (row g V + v is
+def marginal_entropy(z, groups, views, want_probs=False):
+    """MEMO's loss (Zhang, Levine, Finn, NeurIPS 2022) beside entropy: z holds `views` consecutive rows per sample (row g V + v is
     view v of sample g); the loss is the mean over the samples of the entropy of the sample's mean prediction over its views.
     stil_marginal_entropy_groups forms lse, the marginals (through a log-sum-exp over the views, never the logarithm of an
-    underflowed mean), their entropies and dZ / groups.  -> loss; info = dict(marginal [G, K], marginal_entropy [G], lse, and
-    probs [G V, K] when asked for), all on the device.  Backward scales dZ by the incoming gradient.  With views == 1 it is
-    EntropyFn's loss."""
+    underflowed mean), their entropies and dZ / groups.  With views == 1 it is entropy's loss.
+    -> (mean over the samples of the entropy of the mean prediction over each sample's views [autograd],
+    softmax(z) [no grad] when asked for or None, info); info = dict(marginal [G, K], marginal_entropy [G], lse), all on the device."""
+    info = {}
+    groups, views = int(groups), int(views)
 
-    @staticmethod
-    def forward(ctx, z, groups, views, want_probs, info):
+    def launch(z):
         _chk(z)
         R, K = z.shape
         if R != groups * views:
             raise ValueError(f"marginal_entropy: {R} rows are not {groups} samples x {views} views")
-        dev = z.device
-        lse = torch.empty((R,), dtype=torch.float64, device=dev)
+        lse = _empty(z, R, torch.float64)
         p = torch.empty_like(z) if want_probs else None
-        pbar = torch.empty((groups, K), dtype=torch.float32, device=dev)
-        hbar = torch.empty((groups,), dtype=torch.float32, device=dev)
+        pbar = torch.empty((groups, K), dtype=torch.float32, device=z.device)
+        hbar, out = _empty(z, groups, torch.float32), _empty(z, 1, torch.float32)
         dz = torch.empty_like(z)
-        out = torch.empty((1,), dtype=torch.float32, device=dev)
-        ws = torch.empty((groups * (K + (K + 255) // 256),), dtype=torch.float64, device=dev)
+        ws = _empty(z, groups * (K + (K + 255) // 256), torch.float64)
         lib().marginal_entropy_groups(_p(z), K, groups, views, K, 1.0 / groups, _p(lse), _p(p), K, _p(pbar), K, _p(hbar), _p(dz), K,
                                       _p(out), _p(ws), _stream())
-        info.update(marginal=pbar, marginal_entropy=hbar, lse=lse, probs=p)
-        ctx.save_for_backward(dz)
-        return out[0]
+        info.update(marginal=pbar, marginal_entropy=hbar, lse=lse)
+        return out[0], p, dz
 
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return _scale_by(dz, g), None, None, None, None
-
-
-def marginal_entropy(z, groups, views, want_probs=False):
-    """-> (mean over the samples of the entropy of the mean prediction over each sample's views [autograd],
-    softmax(z) [no grad] or None, info)"""
-    info = {}
-    loss = MarginalEntropyFn.apply(z.contiguous(), int(groups), int(views), bool(want_probs), info)
-    return loss, info.pop("probs"), info
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
 def argmax_ce(z):
@@ -467,6 +410,11 @@ class CompactState(TentState):
     def _compact_views(self, buf):
         return [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._spans, self.tensors)]
 
+    def _slab_args(self):
+        """what every slab entry point takes to find A's chunks: achunks, n_achunks, chunk2tensor, active, n_tensors, n"""
+        f = self.flat
+        return _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total
+
     @torch.no_grad()
     def snapshot(self):
         self.source = self._compact_views(self.theta0)
@@ -502,17 +450,13 @@ class EataState(CompactState):
     @torch.no_grad()
     def fisher_accum(self, scale: float):
         """fisher += grads^2 * scale over A's chunks of this state's gradient slab"""
-        f = self.flat
-        lib().eata_fisher_accum(_p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks, _p(f.chunk2tensor),
-                                _p(self.active), len(f.tensors), f.total, float(scale), _stream())
+        lib().eata_fisher_accum(_p(self.fisher), _p(self.grads), *self._slab_args(), float(scale), _stream())
 
     @torch.no_grad()
     def anchor(self, alpha: float, out: torch.Tensor):
         """grads += 2 alpha F (theta - theta0) over A's chunks; out[0] = alpha sum F (theta - theta0)^2"""
-        f = self.flat
-        lib().eata_anchor(_p(f.params), _p(self.theta0), _p(self.fisher), _p(self.grads), _p(self.achunks), self.n_achunks,
-                          _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total, float(alpha), _p(self.partial), _p(out),
-                          _stream())
+        lib().eata_anchor(_p(self.flat.params), _p(self.theta0), _p(self.fisher), _p(self.grads), *self._slab_args(), float(alpha),
+                          _p(self.partial), _p(out), _stream())
 
     def fisher_tensors(self) -> List[torch.Tensor]:
         return [v.clone() for v in self._compact_views(self.fisher)]
@@ -554,10 +498,6 @@ class SarState(CompactState):
         self.ema.zero_()
         self.ema_valid.zero_()
         self.recover.zero_()
-
-    def _slab_args(self):
-        f = self.flat
-        return _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total
 
     @torch.no_grad()
     def perturb(self, rho: float):
@@ -690,6 +630,13 @@ def _forward(model, x_img, x_tab):
         return model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
 
 
+def _score_forward(model, x_img, x_tab):
+    """The forward of `_forward` alone, under no_grad on the layouts of the current weights -> out_m"""
+    with torch.no_grad():
+        model.flat.refresh_layouts(student=True, teacher=False)
+        return _forward(model, x_img, x_tab)
+
+
 @contextlib.contextmanager
 def _grads_of(model, st):
     """requires_grad on A only, no gradient collectives (adaptation is per rank), layouts of the current weights, grad mode on
@@ -722,6 +669,11 @@ def adapting_pass(model, x, st, loss_fn):
     return out_m.detach(), loss.detach(), probs, extras
 
 
+def _e_margin(hp):
+    """tta_e_margin resolved: None -> 0.4 ln K, EATA's published fraction of the maximal entropy"""
+    return 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+
+
 def tent_step(model, batch):
     """TENT (Wang et al., ICLR 2021) on one test batch: forward with batch-statistics BatchNorm (running buffers untouched,
     no MI-layer dropout), loss = mean row entropy of softmax(out_m), gradients for A only (no weight-gradient products),
@@ -751,7 +703,7 @@ def eata_step(model, batch):
     hp = model.hp
     with torch.inference_mode(False):
         st = _begin(model)
-        e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+        e0 = _e_margin(hp)
         out_m, loss_ent, probs, info = adapting_pass(model, x, st, lambda z: eata_entropy(
             z, e0, hp.tta_d_margin, hp.tta_probs_momentum, st.m, st.m_valid, st.active, st.gate))
         loss_anchor = torch.zeros((1,), dtype=torch.float32, device=out_m.device)
@@ -824,10 +776,8 @@ def marginal_entropy_step(model, batch):
         views, tab_rep, draws = make_views(model, (x_img, x_tab))
         _, loss, _, info = adapting_pass(model, (views, tab_rep), st, lambda z: marginal_entropy(z, B, V))
         st.adam_step(hp.tta_lr)
-        with torch.no_grad():
-            model.flat.refresh_layouts(student=True, teacher=False)
-            out_m = _forward(model, x_img, x_tab)
-            probs = ops.softmax_rows(out_m)
+        out_m = _score_forward(model, x_img, x_tab)
+        probs = ops.softmax_rows(out_m)
         model.last_tta = dict(loss=loss, marginal=info["marginal"], marginal_entropy=info["marginal_entropy"], y_hat_m=out_m,
                               probs=probs, draws=draws)
         return model._score_test(probs, y)
@@ -856,12 +806,9 @@ def deyo_step(model, batch):
         perm = st.draw(x_img.shape[0], g)
         if not np.array_equal(np.sort(perm, axis=1), np.broadcast_to(np.arange(g * g, dtype=np.int32), perm.shape)):
             raise RuntimeError("deyo_step: a drawn row is not a permutation of the patch slots")
-        lnk = math.log(hp.num_classes)
-        tau = 0.5 * lnk if hp.tta_ent_margin is None else float(hp.tta_ent_margin)
-        e0 = 0.4 * lnk if hp.tta_e_margin is None else float(hp.tta_e_margin)
-        with torch.no_grad():
-            model.flat.refresh_layouts(student=True, teacher=False)
-            zs = _forward(model, patch_shuffle(x_img, g, st.upload(perm)), x_tab)
+        tau = 0.5 * math.log(hp.num_classes) if hp.tta_ent_margin is None else float(hp.tta_ent_margin)
+        e0 = _e_margin(hp)
+        zs = _score_forward(model, patch_shuffle(x_img, g, st.upload(perm)), x_tab)
         out_m, loss, probs, info = adapting_pass(model, (x_img, x_tab), st, lambda z: deyo_entropy(
             z, zs, tau, hp.tta_plpd_margin, e0, hp.tta_reweight_ent, hp.tta_reweight_plpd, st.active, st.gate))
         st.adam_step(hp.tta_lr, mask=st.gate)
@@ -903,7 +850,7 @@ def sar_step(model, batch):
     hp = model.hp
     with torch.inference_mode(False):
         st = _begin(model)
-        e0 = 0.4 * math.log(hp.num_classes) if hp.tta_e_margin is None else float(hp.tta_e_margin)
+        e0 = _e_margin(hp)
         c = sar_reset_value(hp)
         xs = _inputs(model, x)
         out_m, loss1, probs, i1 = adapting_pass(model, xs, st, lambda z: sar_entropy(z, e0))
@@ -930,12 +877,15 @@ def bn_adapt_step(model, batch):
     x, y = batch
     with torch.inference_mode(False), torch.no_grad():
         model.setup_device()
-        x_img, x_tab = _inputs(model, x)
-        model.flat.refresh_layouts(student=True, teacher=False)
-        out_m = _forward(model, x_img, x_tab)
+        out_m = _score_forward(model, *_inputs(model, x))
         probs = ops.softmax_rows(out_m)
         model.last_tta = dict(y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
+
+
+STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
+         "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step}   # tta_method -> STiLModel.test_step's body
+METHODS = (None,) + tuple(STEPS)
 
 
 # ---------------------------------------------------------------------------------------------- EATA's Fisher estimate
