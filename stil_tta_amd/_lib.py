@@ -1,5 +1,5 @@
-"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h and the test-time adaptation headers (TTA_HEADERS) at
-import time.
+"""ctypes binding of libstil_hip.so, generated from include/stil_hip.h, the test-time adaptation headers (TTA_HEADERS) and the
+headers kept beside their kernels (MEMORY_HEADERS) at import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -16,6 +16,8 @@ _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "stil_hip.h")
 # test-time adaptation, one header per method, kept out of stil_hip.h's ledger: tests/test_tta_abi_ledger_cpu.py holds theirs
 TTA_HEADERS = tuple(os.path.join(_ROOT, "include", f"stil_{n}.h") for n in ("tta", "eata", "bnprior", "infomax", "margent", "deyo", "sar"))
+# headers kept beside their kernels in csrc/ (include/ is a closed set): tests/test_bnmemory_abi_ledger_cpu.py holds their ledger
+MEMORY_HEADERS = (os.path.join(_HERE, "csrc", "stil_bnmemory.h"),)
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -88,7 +90,7 @@ class _Lib:
                                f"(or `make -C {CSRC}`) first; there is no fallback path")
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
-        for header in TTA_HEADERS:
+        for header in TTA_HEADERS + MEMORY_HEADERS:
             self.protos.update(parse_header(header))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks

@@ -21,6 +21,7 @@ extern "C" int stil_device_count(void) {
 #include "gemm.hip"
 #include "bn.hip"
 #include "bn_prior.hip"
+#include "bn_memory.hip"
 #include "transformer.hip"
 #include "loss.hip"
 #include "saint.hip"

@@ -652,6 +652,36 @@ class bn_prior:
         _bn_prior = self.prev
 
 
+_bn_memory = None   # the innermost ops.bn_memory scope
+
+
+class bn_memory:
+    """with ops.frozen_bn_stats(), ops.bn_memory(mem, rho, alpha, unbiased, update): the conv+BN layers normalise by
+    (1 - rho) memory + rho batch statistics, the memory being a running estimate of the TARGET statistics that the adaptation owns
+    (RoTTA's robust BatchNorm, Yuan et al., CVPR 2023; DUA, Mirza et al., CVPR 2022) instead of the checkpoint's running buffers,
+    which are neither read nor written.  mem.layer(running_mean) -> (mean, var, mean_out, var_out), the layer's [C] views of the
+    estimate the step reads and of the one it writes, found by the layer's running_mean tensor.  With `update` the layer also
+    writes mean_out <- (1 - alpha) mean + alpha batch mean, var_out <- (1 - alpha) var + alpha batch variance (unbiased: times
+    M / (M - 1)); without, nothing is written and alpha is unused (stil_bn_memory_fwd(_tiles), csrc/stil_bnmemory.h).  The backward is
+    ops.bn_prior's at the same rho: the memory is a constant of the step.  Takes the place of ops.bn_prior, not a seat beside it."""
+
+    def __init__(self, mem, rho, alpha, unbiased=False, update=True):
+        rho, alpha = float(rho), float(alpha)
+        if not (0.0 <= rho <= 1.0 and 0.0 <= alpha <= 1.0):   # false for NaN
+            raise ValueError(f"ops.bn_memory: rho={rho!r} and alpha={alpha!r} must lie in [0, 1]")
+        self.mem, self.rho, self.alpha, self.unbiased, self.update = mem, rho, alpha, bool(unbiased), bool(update)
+
+    def __enter__(self):
+        global _bn_memory
+        if _bn_prior is not None:
+            raise RuntimeError("ops.bn_memory takes the place of ops.bn_prior: the two scopes do not nest")
+        self.prev, _bn_memory = _bn_memory, self
+
+    def __exit__(self, *exc):
+        global _bn_memory
+        _bn_memory = self.prev
+
+
 class ConvBnActFn(torch.autograd.Function):
     """z = relu?( BN_train(conv(x, w)) + residual? ) on NHWC activations.
 
@@ -719,8 +749,16 @@ class ConvBnActFn(torch.autograd.Function):
         assert fused or not defer, "deferred BatchNorm needs the epilogue statistics (can_defer_bn)"
         # deferred: no z.  Under parity tracing the tests still want this layer's ReLU decisions: z is materialised for them
         z = None if (defer and _trace is None) else torch.empty((M, Cout), dtype=torch.float32, device=dev)
-        rho = delta = None
-        if _bn_prior is not None:   # source-statistics prior: the running buffers are read, never written
+        rho = delta = mem = None
+        if _bn_memory is not None:   # the adaptation's own estimate of the target statistics: the running buffers only name the layer
+            if not _bn_frozen or rmean is None or _bn_prior is not None:
+                raise RuntimeError("ops.bn_memory belongs inside ops.frozen_bn_stats, without ops.bn_prior, and needs the layer's running_mean")
+            mem = _bn_memory
+            rho, delta = mem.rho, torch.empty((Cout,), dtype=torch.float32, device=dev)
+            src_mean, src_var, out_mean, out_var = mem.mem.layer(rmean)
+            if not mem.update:
+                out_mean = out_var = None
+        elif _bn_prior is not None:   # source-statistics prior: the running buffers are read, never written
             if not _bn_frozen or rmean is None or rvar is None:
                 raise RuntimeError("ops.bn_prior belongs inside ops.frozen_bn_stats and needs the layer's running statistics")
             rho, delta = _bn_prior, torch.empty((Cout,), dtype=torch.float32, device=dev)
@@ -730,7 +768,11 @@ class ConvBnActFn(torch.autograd.Function):
         if fused:
             nb = lib().bn_tiles_workspace_bytes(M, Cout, tile_rows)
             ws = _ws.get(nb, dev)
-            if rho is not None:
+            if mem is not None:
+                lib().bn_memory_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(src_mean), _p(src_var), _p(out_mean), _p(out_var),
+                                          mem.alpha, int(mem.unbiased), rho, _p(resid), _p(rstats), _p(z), _p(stats), _p(delta), M, Cout,
+                                          1 if relu else 0, 1e-5, _p(ws), nb, _stream())
+            elif rho is not None:
                 lib().bn_prior_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(rstats),
                                          _p(z), _p(stats), _p(delta), M, Cout, 1 if relu else 0, 1e-5, _p(ws), nb, _stream())
             else:
@@ -740,7 +782,11 @@ class ConvBnActFn(torch.autograd.Function):
             assert rstats is None
             nb = lib().bn_workspace_bytes(M, Cout)
             ws = _ws.get(nb, dev)
-            if rho is not None:
+            if mem is not None:
+                lib().bn_memory_fwd(_p(y), _p(gamma), _p(beta), _p(src_mean), _p(src_var), _p(out_mean), _p(out_var), mem.alpha,
+                                    int(mem.unbiased), rho, _p(resid), _p(z), _p(stats), _p(delta), M, Cout, 1 if relu else 0, 1e-5,
+                                    _p(ws), nb, _stream())
+            elif rho is not None:
                 lib().bn_prior_fwd(_p(y), _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(z), _p(stats), _p(delta), M, Cout,
                                    1 if relu else 0, 1e-5, _p(ws), nb, _stream())
             else:

@@ -48,6 +48,7 @@ _DEFAULTS = dict(
     tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
                          # | "shot_im" (Liang et al., ICML 2020: entropy plus a batch-diversity term) | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
                          # | "marginal_entropy" (MEMO, Zhang et al., NeurIPS 2022: adapts on augmented views of each sample, scores the clean batch after the update)
+                         # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
@@ -77,6 +78,12 @@ _DEFAULTS = dict(
     tta_sar_rho=0.05,              # rho: the radius of the ascent step over A between the two passes (the paper's default); 0: no perturbation
     tta_sar_reset=None,            # A returns to its source values when the running mean of the loss falls below it; None = 0.2 ln(num_classes) / ln(1000)
                                    # (the paper's ImageNet 0.2 at the same fraction of the maximal entropy: this project's scaling); False: no recovery
+    # every method: a running estimate of the TARGET BatchNorm statistics, owned by the adaptation (tta.BnMemory), never written into the checkpoint
+    tta_bn_momentum=None,          # alpha in (0, 1]: every adapting forward normalises on the estimate (it replaces the checkpoint statistics as tta_bn_prior's
+                                   # source; without tta_bn_prior the layer normalises by exactly the updated estimate: RoTTA's robust BatchNorm, Yuan et al.,
+                                   # CVPR 2023, alpha = 0.05) and one forward per batch updates it.  None: no estimate is kept.  "dua" (Mirza et al., CVPR 2022) needs it
+    tta_bn_momentum_decay=1.0,     # omega and alpha_min of DUA's schedule: the t-th update (t = 1, 2, ...) uses alpha_t = min(1, alpha omega^t + alpha_min);
+    tta_bn_momentum_min=0.0,       # DUA as published (values as recalled: unpinned): batches of 1, tta_views 64, 0.1 / 0.94 / 0.005
 )
 
 
@@ -190,6 +197,7 @@ class STiLModel(_Base):
         self.best_val_score = 0
         self.flat: Optional[FlatState] = None
         self._tent: Optional[tta.TentState] = None        # the adaptation state (tta.py): created by the first adapted batch / Fisher estimate
+        self._bn_mem: Optional[tta.BnMemory] = None       # the running estimate of the target BatchNorm statistics (tta_bn_momentum): independent of _tent
         self.last_tta: Dict[str, torch.Tensor] = {}       # the latest adapted batch: loss, out_m, softmax(out_m)
         tta.check_hparams(hp)
         self.register_load_state_dict_post_hook(lambda *_: tta.drop(self))
@@ -659,7 +667,10 @@ class STiLModel(_Base):
         With "deyo" (tta.deyo_step) a second, forward-only pass on the patch-shuffled images decides together with the entropy
         which rows adapt the model; the scores are those of the clean adapting forward, before the update.
         With "sar" (tta.sar_step) the batch runs two adapting passes, the second at A + tta_sar_rho g / |g|, and A recovers its
-        source values when the running mean of the loss falls below tta_sar_reset; the scores are the first pass's."""
+        source values when the running mean of the loss falls below tta_sar_reset; the scores are the first pass's.
+        With "dua" (tta.dua_step) the running estimate of the BatchNorm statistics takes one update from tta_views augmented views
+        of the batch and the clean batch is then scored in eval mode on that estimate: forward only, nothing else is adapted.
+        With tta_bn_momentum every method normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)
         with torch.no_grad():
@@ -686,7 +697,8 @@ class STiLModel(_Base):
         return tta.param_names(self)
 
     def reset_tta(self):
-        """A <- its source values, the adaptation state cleared, EATA's Fisher estimate kept (tta.reset)."""
+        """A <- its source values, the adaptation state cleared, EATA's Fisher estimate kept; the running estimate of the BatchNorm
+        statistics (tta_bn_momentum) returns to the checkpoint's (tta.reset)."""
         tta.reset(self)
 
     def estimate_tta_fisher(self, batches, max_batches: Optional[int] = None):

@@ -16,6 +16,11 @@ Every method but SAR is ONE adapting pass (`adapting_pass`) with its own loss an
                            Adam over A gated by n > 0 -> recovery of A when the running mean of the loss falls below tta_sar_reset
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
+    dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
+                           (DUA, Mirza et al., CVPR 2022) -> the clean batch scored in eval mode on the memory: no gradient
+With tta_bn_momentum every forward above normalises on the BatchNorm memory (`BnMemory`, model._bn_mem: a running estimate of the
+target statistics in RoTTA's manner, Yuan et al., CVPR 2023) in place of the checkpoint's statistics: all forwards of a batch read
+the same estimate, exactly one of them writes the update, and the step commits it at its end.
 A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState`) lives in
 `model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
 shuffles (`DeyoState.rng`).
@@ -79,6 +84,14 @@ def check_hparams(hp):
     _int_from(hp, "tta_shuffle_seed", 0)
     _number(hp, "tta_sar_rho", 0)
     _number(hp, "tta_sar_reset", 0, strict=True, also=(None, False))   # True is refused: False alone switches recovery off
+    _number(hp, "tta_bn_momentum", 0, strict=True, also=(None,))
+    _number(hp, "tta_bn_momentum_decay", 0, strict=True)
+    _number(hp, "tta_bn_momentum_min", 0)
+    for key, v in (("tta_bn_momentum", hp.tta_bn_momentum), ("tta_bn_momentum_decay", hp.tta_bn_momentum_decay), ("tta_bn_momentum_min", hp.tta_bn_momentum_min)):
+        if v is not None and v > 1:
+            raise ValueError(f"{key} must not exceed 1, not {v!r}")
+    if hp.tta_method == "dua" and hp.tta_bn_momentum is None:
+        raise ValueError("tta_method 'dua' adapts the running estimate of the BatchNorm statistics alone: set tta_bn_momentum (DUA: 0.1)")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -555,6 +568,97 @@ class DeyoState(TentState):
         return out
 
 
+def bn_momentum(hp, t: int) -> float:
+    """alpha_t of the t-th update of the BatchNorm memory, t = 1, 2, ...: min(1, tta_bn_momentum x tta_bn_momentum_decay^t +
+    tta_bn_momentum_min), DUA's schedule (Mirza et al., CVPR 2022); with the default decay 1 and minimum 0 it is tta_bn_momentum."""
+    return min(1.0, float(hp.tta_bn_momentum) * float(hp.tta_bn_momentum_decay) ** int(t) + float(hp.tta_bn_momentum_min))
+
+
+class BnMemory:
+    """The running estimate of the TARGET BatchNorm statistics of model.encoder_imaging (tta_bn_momentum; RoTTA's robust
+    BatchNorm, Yuan et al., CVPR 2023; DUA, Mirza et al., CVPR 2022), held in model._bn_mem beside and independent of TentState:
+    two [2, sum C] float32 buffers (row 0 the means, row 1 the variances) with one [C] view per layer and row.  Every forward of a
+    batch READS the front buffer; the one forward that updates the estimate WRITES the back buffer (ops.bn_memory's `update`), and
+    commit() swaps the two at the end of the step and counts the update in `t`, on the host: nothing is read back.  `alpha` is the
+    momentum of the current batch (bn_momentum(hp, t + 1), set by begin()).  load_source() copies the layers' running buffers into
+    the front buffer and zeroes t; the model's running_mean / running_var / num_batches_tracked are read there and never written.
+    `views`: dua_step's ImageAugmenter, seeded once (tta_view_seed): load_source() leaves its generator running."""
+
+    def __init__(self, model):
+        hp = model.hp
+        self.layers = [mod for mod in model.model.encoder_imaging.modules() if isinstance(mod, nn.BatchNorm2d)]
+        total = sum(mod.num_features for mod in self.layers)
+        dev = self.layers[0].running_mean.device
+        self.bufs = [torch.zeros((2, total), dtype=torch.float32, device=dev) for _ in range(2)]
+        self._views = [{}, {}]   # per buffer: running_mean.data_ptr() of the layer -> (mean [C], var [C])
+        o = 0
+        for mod in self.layers:
+            C = mod.num_features
+            for buf, views in zip(self.bufs, self._views):
+                views[mod.running_mean.data_ptr()] = (buf[0, o:o + C], buf[1, o:o + C])
+            o += C
+        self.front, self.t, self.alpha = 0, 0, bn_momentum(hp, 1)
+        self.views = None
+        if hp.tta_method == "dua":
+            from .augment import ImageAugmenter
+            self.views = ImageAugmenter(img_size=hp.img_size, target=hp.target, kind=hp.tta_view_policy, augmentation_rate=1.0,
+                                        seed=hp.tta_view_seed, augmentation_speedup=False)
+        self.load_source()
+
+    def _pairs(self, which):
+        return [self._views[which][mod.running_mean.data_ptr()] for mod in self.layers]
+
+    @torch.no_grad()
+    def load_source(self):
+        pairs = self._pairs(self.front)
+        torch._foreach_copy_([p[0] for p in pairs] + [p[1] for p in pairs],
+                             [mod.running_mean for mod in self.layers] + [mod.running_var for mod in self.layers])
+        self.t = 0
+
+    def begin(self, hp):
+        """before the first forward of a batch: under tta_episodic the estimate returns to the checkpoint's; alpha <- alpha_(t+1)"""
+        if hp.tta_episodic:
+            self.load_source()
+        self.alpha = bn_momentum(hp, self.t + 1)
+
+    def layer(self, running_mean):
+        """-> (mean, var) to read and (mean, var) to write, [C] views, of the layer that owns `running_mean`"""
+        key = running_mean.data_ptr()
+        try:
+            return self._views[self.front][key] + self._views[1 - self.front][key]
+        except KeyError:
+            raise RuntimeError("BnMemory: this BatchNorm layer is not one the memory was built over (the model's buffers moved since; "
+                               "tta.drop(model) forgets the memory, the next batch rebuilds it)") from None
+
+    def commit(self):
+        self.front, self.t = 1 - self.front, self.t + 1
+
+    def state(self):
+        """-> [(mean, var)] per layer, in encoder_imaging's module order: copies of the current estimate"""
+        return [(m.clone(), v.clone()) for m, v in self._pairs(self.front)]
+
+
+def _memory(model) -> Optional[BnMemory]:
+    """model._bn_mem when tta_bn_momentum is set (created on first use, the model being on its device), else None"""
+    if model.hp.tta_bn_momentum is None:
+        return None
+    if model._bn_mem is None:
+        model._bn_mem = BnMemory(model)
+    return model._bn_mem
+
+
+def _begin_memory(model) -> Optional[BnMemory]:
+    mem = _memory(model)
+    if mem is not None:
+        mem.begin(model.hp)
+    return mem
+
+
+def _commit_memory(model):
+    if model._bn_mem is not None and model.hp.tta_bn_momentum is not None:
+        model._bn_mem.commit()
+
+
 def _state(model) -> TentState:
     """model._tent, created on first use (the model is on its device)"""
     if model._tent is None:
@@ -591,23 +695,29 @@ def _begin(model) -> TentState:
         st.reset()
     if st.source is None:
         st.snapshot()
+    _begin_memory(model)
     return st
 
 
 def drop(model):
     """Forget the adaptation state (moments, step counts, source values; EATA's running mean of predictions and its Fisher
-    estimate, which belongs to the weights it was estimated on): load_state_dict calls this."""
+    estimate, which belongs to the weights it was estimated on; the running estimate of the BatchNorm statistics): load_state_dict
+    calls this."""
     model._tent = None
+    model._bn_mem = None
 
 
 def reset(model):
     """A <- its source values (A as it stood at the first adapted batch since construction / load_state_dict / reset),
     moments and step counts cleared; the next adapted batch takes the source values afresh.  EATA: the running mean of
-    the selected predictions is cleared too, the Fisher estimate is kept.  SAR: the running mean of the loss is forgotten too."""
-    if model._tent is not None:
-        with torch.inference_mode(False):
+    the selected predictions is cleared too, the Fisher estimate is kept.  SAR: the running mean of the loss is forgotten too.
+    The running estimate of the BatchNorm statistics (tta_bn_momentum) returns to the checkpoint's and its update count to 0."""
+    with torch.inference_mode(False):
+        if model._tent is not None:
             model._tent.reset()
             model._tent.source = None
+        if model._bn_mem is not None:
+            model._bn_mem.load_source()
 
 
 # ---------------------------------------------------------------------------------------------- the adapting pass
@@ -621,20 +731,30 @@ def _inputs(model, x):
     return x_img, x_tab
 
 
-def _forward(model, x_img, x_tab):
-    """The adapting forward -> out_m: no MI-layer dropout; BatchNorm over the B images of this batch by batch statistics,
-    running buffers untouched; with tta_bn_prior = N blended with the source statistics at rho = B / (N + B) (a short last
-    batch gets its own rho)."""
+def _bn_scope(model, B, update):
+    """The BatchNorm rule of an adapting forward on B images.  Without tta_bn_momentum: the batch statistics, under tta_bn_prior = N
+    blended with the checkpoint's at rho = B / (N + B).  With it the memory (model._bn_mem, the estimate as the batch found it) takes
+    the checkpoint's place: rho = B / (N + B) under tta_bn_prior = N, otherwise rho = alpha_t, i.e. the layer normalises by exactly
+    the updated estimate (RoTTA); `update`: this forward is the one of its batch that writes the update (biased variance)."""
     N = model.hp.tta_bn_prior
-    with ops.frozen_bn_stats(), (contextlib.nullcontext() if N is None else ops.bn_prior(N, x_img.shape[0])):
+    mem = _memory(model)
+    if mem is None:
+        return contextlib.nullcontext() if N is None else ops.bn_prior(N, B)
+    return ops.bn_memory(mem, mem.alpha if N is None else B / (N + B), mem.alpha, unbiased=False, update=update)
+
+
+def _forward(model, x_img, x_tab, update=False):
+    """The adapting forward -> out_m: no MI-layer dropout; BatchNorm over the B images of this batch by `_bn_scope`'s rule (a short
+    last batch gets its own rho), running buffers untouched."""
+    with ops.frozen_bn_stats(), _bn_scope(model, x_img.shape[0], update):
         return model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
 
 
-def _score_forward(model, x_img, x_tab):
+def _score_forward(model, x_img, x_tab, update=False):
     """The forward of `_forward` alone, under no_grad on the layouts of the current weights -> out_m"""
     with torch.no_grad():
         model.flat.refresh_layouts(student=True, teacher=False)
-        return _forward(model, x_img, x_tab)
+        return _forward(model, x_img, x_tab, update)
 
 
 @contextlib.contextmanager
@@ -656,14 +776,15 @@ def _grads_of(model, st):
             q.requires_grad_(f)
 
 
-def adapting_pass(model, x, st, loss_fn):
+def adapting_pass(model, x, st, loss_fn, update=True):
     """One adapting forward and backward on the inputs x = (images, table, ...) of a batch: the forward of `_forward`,
     loss_fn(out_m) -> (loss, probs, extras), gradients of the loss for A only (no weight-gradient products) in st.grads.
-    Writes st.grads and whatever loss_fn writes; never a parameter, BatchNorm buffer, teacher, prototype or training slab.
+    Writes st.grads and whatever loss_fn writes and, with tta_bn_momentum and `update`, the back buffer of the BatchNorm memory
+    (a constant of the backward); never a parameter, BatchNorm buffer, teacher, prototype or training slab.
     The caller holds torch.inference_mode(False).  -> (out_m, loss, probs, extras), detached."""
     x_img, x_tab = _inputs(model, x)
     with _grads_of(model, st):
-        out_m = _forward(model, x_img, x_tab)
+        out_m = _forward(model, x_img, x_tab, update)
         loss, probs, extras = loss_fn(out_m)
         loss.backward()
     return out_m.detach(), loss.detach(), probs, extras
@@ -685,6 +806,7 @@ def tent_step(model, batch):
         st = _begin(model)
         out_m, loss, probs, _ = adapting_pass(model, x, st, entropy)
         st.adam_step(model.hp.tta_lr)
+        _commit_memory(model)
         model.last_tta = dict(loss=loss, y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
 
@@ -710,6 +832,7 @@ def eata_step(model, batch):
         if st.fisher is not None:
             st.anchor(hp.tta_fisher_alpha, loss_anchor)
         st.adam_step(hp.tta_lr, mask=st.gate)
+        _commit_memory(model)
         model.last_tta = dict(loss=loss_ent + loss_anchor[0], y_hat_m=out_m, probs=probs, n_selected=info["counts"][0],
                               n_reliable=info["counts"][1], loss_entropy=loss_ent, loss_anchor=loss_anchor[0],
                               selected=info["sel"], reliable=info["rel"], entropy=info["H"], cos=info["cos"], weight=info["w"])
@@ -729,23 +852,24 @@ def shot_im_step(model, batch):
         st = _begin(model)
         out_m, loss, probs, info = adapting_pass(model, x, st, lambda z: infomax(z, hp.tta_div_weight, hp.tta_div_eps))
         st.adam_step(hp.tta_lr)
+        _commit_memory(model)
         model.last_tta = dict(loss=loss, loss_entropy=info["loss_entropy"], loss_diversity=info["loss_diversity"],
                               marginal=info["marginal"], y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
 
 
 def make_views(model, x, draws=None):
-    """The views marginal_entropy_step adapts on, from the inputs x = (images [B, 3, H, W], table [B, C], ...) of a batch:
+    """The views marginal_entropy_step adapts on (and dua_step takes its statistics from), from the inputs x = (images [B, 3, H, W], table [B, C], ...) of a batch:
     every image repeated tta_views times, sample-major (row g V + v is view v of sample g), and augmented by the model-owned
     ImageAugmenter (family tta_view_policy, every row augmented, seeded by tta_view_seed when the adaptation state is created);
     the table rows repeated UNCHANGED (the model holds no table to draw corrupted cells from).  draws: the host draws of an
     earlier call (last_tta["draws"]), which rebuild its views bit for bit and leave the generator alone; None draws afresh.
     -> (views [B V, 3, P, P], table [B V, C], draws)"""
-    if model.hp.tta_method != "marginal_entropy":
-        raise ValueError(f"augmented views belong to tta_method 'marginal_entropy' (this model: {model.hp.tta_method!r})")
+    if model.hp.tta_method not in ("marginal_entropy", "dua"):
+        raise ValueError(f"augmented views belong to tta_method 'marginal_entropy' and 'dua' (this model: {model.hp.tta_method!r})")
     with torch.inference_mode(False), torch.no_grad():
         model.setup_device()
-        aug = _state(model).views
+        aug = _memory(model).views if model.hp.tta_method == "dua" else _state(model).views   # dua holds no TentState
         x_img, x_tab = _inputs(model, x)
         V = model.hp.tta_views
         B, _, H, W = x_img.shape
@@ -776,6 +900,7 @@ def marginal_entropy_step(model, batch):
         views, tab_rep, draws = make_views(model, (x_img, x_tab))
         _, loss, _, info = adapting_pass(model, (views, tab_rep), st, lambda z: marginal_entropy(z, B, V))
         st.adam_step(hp.tta_lr)
+        _commit_memory(model)   # before the scoring forward: this method scores after its update, of the memory too
         out_m = _score_forward(model, x_img, x_tab)
         probs = ops.softmax_rows(out_m)
         model.last_tta = dict(loss=loss, marginal=info["marginal"], marginal_entropy=info["marginal_entropy"], y_hat_m=out_m,
@@ -812,6 +937,7 @@ def deyo_step(model, batch):
         out_m, loss, probs, info = adapting_pass(model, (x_img, x_tab), st, lambda z: deyo_entropy(
             z, zs, tau, hp.tta_plpd_margin, e0, hp.tta_reweight_ent, hp.tta_reweight_plpd, st.active, st.gate))
         st.adam_step(hp.tta_lr, mask=st.gate)
+        _commit_memory(model)
         model.last_tta = dict(loss=loss, n_selected=info["counts"][0], n_reliable=info["counts"][1], entropy=info["H"],
                               plpd=info["plpd"], weight=info["w"], reliable=info["rel"], selected=info["sel"], y_hat_m=out_m,
                               probs=probs, y_hat_shuffled=zs, perm=perm)
@@ -857,11 +983,12 @@ def sar_step(model, batch):
         st.sel1 = i1["sel"]
         st.perturb(hp.tta_sar_rho)
         _, loss2, _, i2 = adapting_pass(model, xs, st, lambda z: sar_entropy(
-            z, e0, st.sel1, st.active, st.gate, st.ema, st.ema_valid, SAR_EMA_MOMENTUM, c, st.recover))
+            z, e0, st.sel1, st.active, st.gate, st.ema, st.ema_valid, SAR_EMA_MOMENTUM, c, st.recover), update=False)
         st.restore()
         st.adam_step(hp.tta_lr, mask=st.gate)
         if c > 0.0:
             st.recover_if_flagged()
+        _commit_memory(model)
         model.last_tta = dict(loss=loss2, loss_first=loss1, n_selected=i2["counts"][0], n_first=i1["counts"][0],
                               n_reliable=i2["counts"][1], grad_norm=st.norm[0].clone(), ema=st.ema[0].clone(),
                               ema_valid=st.ema_valid[0].clone(), recovered=st.recover[0].clone(), entropy=i1["H"],
@@ -872,19 +999,55 @@ def sar_step(model, batch):
 def bn_adapt_step(model, batch):
     """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
     statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
-    No adapted set, no gradient, no optimiser, no state: reset_tta() and tta_episodic have nothing to act on.  Writes
-    acc_test / auc_test and last_tta, nothing else; Adam never runs."""
+    No adapted set, no gradient, no optimiser, no TentState: without tta_bn_momentum reset_tta() and tta_episodic have nothing to
+    act on; with it this forward is the one that updates the BatchNorm memory, which they return to the checkpoint's statistics.
+    Writes acc_test / auc_test, last_tta and that memory, nothing else; Adam never runs."""
     x, y = batch
     with torch.inference_mode(False), torch.no_grad():
         model.setup_device()
-        out_m = _score_forward(model, *_inputs(model, x))
+        _begin_memory(model)
+        out_m = _score_forward(model, *_inputs(model, x), update=True)
+        _commit_memory(model)
         probs = ops.softmax_rows(out_m)
         model.last_tta = dict(y_hat_m=out_m, probs=probs)
         return model._score_test(probs, y)
 
 
+def dua_step(model, batch):
+    """DUA (Mirza et al., CVPR 2022, "The norm must go on") on one test batch of B samples, B = 1 being the case it is made for.
+    Forward only: no adapted set, no gradient, no optimiser, no TentState; the BatchNorm memory (BnMemory) is all that adapts.
+    (1) V = tta_views augmented views of every sample (make_views; the augmenter and its generator, seeded by tta_view_seed, live in
+    the memory); (2) one forward of encoder_imaging, the only part of the model with BatchNorm layers, on the B V views under
+    no_grad in training mode: every layer normalises by the statistics of the views (rho = 1) and moves the memory by
+    alpha_t = min(1, tta_bn_momentum x tta_bn_momentum_decay^t + tta_bn_momentum_min) towards them, UNBIASED variance, which is
+    the training-mode rule of nn.BatchNorm2d the published code relies on; (3) commit; (4) the clean batch scored in eval mode on
+    the memory alone (rho = 0, nothing written); (5) softmax_rows.  tta_bn_prior has no say here.  With B > 1 the samples share one
+    update.  The published setting is a configuration, not the default: batches of 1, tta_views 64, tta_bn_momentum 0.1,
+    tta_bn_momentum_decay 0.94, tta_bn_momentum_min 0.005 (as recalled: unpinned), not episodic.
+    Unlike the paper, on purpose: the views come from this project's own transform families (tta_view_policy), not the paper's
+    augmentation list; and make_views repeats the table row of a sample unchanged for its views (the statistics pass itself reads
+    the images only).
+    last_tta: y_hat_m, probs [B, K] of the scoring forward, on the device; alpha (alpha_t of this batch, a float) and draws, the
+    host dict make_views rebuilds the views from."""
+    x, y = batch
+    with torch.inference_mode(False), torch.no_grad():
+        model.setup_device()
+        mem = _begin_memory(model)
+        x_img, x_tab = _inputs(model, x)
+        views, _, draws = make_views(model, (x_img, x_tab))
+        model.flat.refresh_layouts(student=True, teacher=False)
+        with ops.frozen_bn_stats(), ops.bn_memory(mem, 1.0, mem.alpha, unbiased=True, update=True):
+            model.model.encoder_imaging.run(views, True, None)
+        mem.commit()
+        with ops.frozen_bn_stats(), ops.bn_memory(mem, 0.0, mem.alpha, update=False):
+            out_m = model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+        probs = ops.softmax_rows(out_m)
+        model.last_tta = dict(y_hat_m=out_m, probs=probs, alpha=mem.alpha, draws=draws)
+        return model._score_test(probs, y)
+
+
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
-         "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step}   # tta_method -> STiLModel.test_step's body
+         "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
@@ -914,7 +1077,7 @@ def estimate_fisher(model, batches, max_batches: Optional[int] = None) -> int:
         for batch in batches:
             if seen >= N:
                 break
-            adapting_pass(model, batch[0], st, argmax_ce)
+            adapting_pass(model, batch[0], st, argmax_ce, update=False)
             st.fisher_accum(1.0 / N)
             seen += 1
         if seen < N:  # an iterable shorter than max_batches: the mean is over the batches seen
