@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
   }
 }
 
-// ---- max-pool 3x3 s2 p1 (NHWC).  idx = ky*3+kx of the FIRST maximum in scan order (ATen tie rule).
+// ---- max-pool 3x3 s2 p1 (NHWC).  idx = ky*3+kx of the FIRST maximum in scan order (ATen tie rule; a NaN wins, the last one stays).
 // four channels per thread (C % 4 == 0): 16-byte loads / stores, one (n, oy, ox) decode per 4 elements
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ idx,
                                                            int N, int H, int W, int C, int OH, int OW) {
@@ -448,7 +448,9 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
     const int oy = (int)(t % OH);
     const int n = (int)(t / OH);
     float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    // a window that holds nothing above -inf keeps its starting tap: the first IN-BOUNDS one, as ATen's (pad 1: row / column -1 only)
+    const int first = (oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0);
+    int b0 = first, b1 = first, b2 = first, b3 = first;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
       const int iy = oy * 2 - 1 + ky;

@@ -27,6 +27,7 @@ _MATCH = "test_gpu_match.py"
 _MET = "test_gpu_metrics.py"
 _ATT = "test_gpu_attention.py"
 _ATT_CPU = "test_attention_config_cpu.py"
+KE = "test_gpu_kernel_edges.py"
 
 # name -> list of "file::function" (checked directly there) | str (the reason it has no test of its own)
 LEDGER = {
@@ -58,8 +59,8 @@ LEDGER = {
     "stil_weight_layouts": [_PLAN],
     "stil_weight_layout_job_bytes": [_PLAN],
     "stil_weight_layout_job_blocks": [_PLAN],
-    "stil_im2col_nchw": [f"{OPS}::test_stem_and_maxpool"],
-    "stil_transpose": [_PLAN],
+    "stil_im2col_nchw": [f"{OPS}::test_stem_and_maxpool", f"{KE}::test_im2col_nchw_equals_unfold"],
+    "stil_transpose": [_PLAN, f"{KE}::test_transpose_equals_t"],
     "stil_bn_workspace_bytes": [_BN_STATS],
     "stil_bn_train_fwd": [_BN_STATS, f"{OPS}::test_conv_bn_act_train_and_eval"],
     "stil_bn_train_fwd_tiles": [_BN_STATS, f"{OPS}::test_deferred_batchnorm_is_the_materialised_path_bit_for_bit"],
@@ -68,12 +69,11 @@ LEDGER = {
     "stil_bn_train_bwd": [_BN_BWD, f"{OPS}::test_conv_bn_act_train_and_eval"],
     "stil_bn_bwd_tiles_workspace_bytes": [_BN_BWD],
     "stil_bn_train_bwd_tiles": [_BN_BWD],
-    "stil_maxpool3x3s2_fwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu"],
-    "stil_maxpool3x3s2_bwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu"],
-    "stil_layernorm_fwd": [f"{OPS}::test_layernorm"],
-    "stil_layernorm_bwd_workspace_bytes": "size of the per-block partials of stil_layernorm_bwd, whose block count is internal; a short workspace is "
-                                          "rejected inside test_layernorm",
-    "stil_layernorm_bwd": [f"{OPS}::test_layernorm"],
+    "stil_maxpool3x3s2_fwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu", f"{KE}::test_maxpool_ties_nan_and_all_minus_inf_windows_route_like_aten"],
+    "stil_maxpool3x3s2_bwd": [f"{OPS}::test_stem_and_maxpool", f"{OPS}::test_maxpool_ties_after_relu", f"{KE}::test_maxpool_ties_nan_and_all_minus_inf_windows_route_like_aten"],
+    "stil_layernorm_fwd": [f"{OPS}::test_layernorm", f"{KE}::test_layernorm_vector_kernels", f"{KE}::test_layernorm_scalar_kernels_by_shape", f"{KE}::test_layernorm_both_instantiations_on_the_same_rows"],
+    "stil_layernorm_bwd_workspace_bytes": [f"{KE}::test_layernorm_bwd_refuses_before_any_write", f"{KE}::test_layernorm_vector_kernels"],
+    "stil_layernorm_bwd": [f"{OPS}::test_layernorm", f"{KE}::test_layernorm_vector_kernels", f"{KE}::test_layernorm_scalar_kernels_by_shape", f"{KE}::test_layernorm_both_instantiations_on_the_same_rows", f"{KE}::test_layernorm_bwd_refuses_before_any_write"],
     "stil_attention_fwd": [f"{_ATT}::test_attention_kernels_against_float64", f"{_ATT}::test_every_kernel_is_reached_in_every_orientation",
                            f"{OPS}::test_attention"],
     "stil_attention_bwd": [f"{_ATT}::test_attention_kernels_against_float64", f"{_ATT}::test_refused_backward_launches_nothing",
@@ -85,8 +85,8 @@ LEDGER = {
     "stil_drop_add": [f"{EP}::test_drop_add_both_paths_all_operand_combinations", f"{EP}::test_drop_add_vector_and_scalar_paths_agree_bit_for_bit",
                       f"{EP}::test_drop_add_backward"],
     "stil_axpby": [f"{EP}::test_axpby_and_scale_dev"],
-    "stil_rng_mask": [f"{OPS}::test_rng_mask_rate_and_determinism"],
-    "stil_counter_inc": [f"{OPS}::test_rng_mask_rate_and_determinism"],
+    "stil_rng_mask": [f"{OPS}::test_rng_mask_rate_and_determinism", f"{KE}::test_rng_mask_equals_the_integer_model_byte_for_byte", f"{KE}::test_rng_mask_offset_continues_the_stream"],
+    "stil_counter_inc": [f"{OPS}::test_rng_mask_rate_and_determinism", f"{KE}::test_rng_mask_equals_the_integer_model_byte_for_byte"],
     "stil_tab_embed_fwd": [f"{OPS}::test_tab_embed"],
     "stil_tab_embed_bwd_workspace_bytes": [_INFO],
     "stil_tab_embed_bwd": [f"{OPS}::test_tab_embed"],
@@ -106,14 +106,14 @@ LEDGER = {
     "stil_scale_dev": [f"{EP}::test_axpby_and_scale_dev"],
     "stil_l2norm_fwd": [f"{EP}::test_l2norm"],
     "stil_l2norm_bwd": [f"{EP}::test_l2norm"],
-    "stil_clip_fwd": [f"{OPS}::test_clip_and_club"],
-    "stil_clip_bwd": [f"{OPS}::test_clip_and_club"],
-    "stil_club_fwd": [f"{OPS}::test_clip_and_club"],
-    "stil_club_bwd": [f"{OPS}::test_clip_and_club"],
-    "stil_cgpl_pgls": [f"{OPS}::test_cgpl_pgls_and_prototypes", f"{OPS}::test_cgpl_top1_is_argmax_of_softmax_with_first_index_ties"],
+    "stil_clip_fwd": [f"{OPS}::test_clip_and_club", f"{KE}::test_clip_fwd_bwd_on_a_logit_matrix"],
+    "stil_clip_bwd": [f"{OPS}::test_clip_and_club", f"{KE}::test_clip_fwd_bwd_on_a_logit_matrix"],
+    "stil_club_fwd": [f"{OPS}::test_clip_and_club", f"{KE}::test_club_against_the_materialised_form"],
+    "stil_club_bwd": [f"{OPS}::test_clip_and_club", f"{KE}::test_club_against_the_materialised_form"],
+    "stil_cgpl_pgls": [f"{OPS}::test_cgpl_pgls_and_prototypes", f"{OPS}::test_cgpl_top1_is_argmax_of_softmax_with_first_index_ties", f"{KE}::test_cgpl_pgls_at_every_width"],
     "stil_da_apply": [f"{EP}::test_da_apply"],
     "stil_proto_loss": [f"{EP}::test_proto_loss", f"{EP}::test_proto_loss_at_its_lds_bound"],
-    "stil_proto_accum": [f"{OPS}::test_cgpl_pgls_and_prototypes"],
+    "stil_proto_accum": [f"{OPS}::test_cgpl_pgls_and_prototypes", f"{KE}::test_proto_accum"],
     "stil_proto_add": [f"{EP}::test_proto_add_and_commit"],
     "stil_proto_commit": [f"{EP}::test_proto_add_and_commit"],
     "stil_contrast_graph": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch"],
@@ -121,10 +121,10 @@ LEDGER = {
     "stil_freematch_update": [f"{_MATCH}::test_freematch_kernels_against_torch"],
     "stil_freematch_entropy": [f"{_MATCH}::test_freematch_kernels_against_torch"],
     "stil_flag_ratios": [f"{EP}::test_flag_ratios"],
-    "stil_onehot_argmax": [f"{OPS}::test_onehot_argmax_first_maximum_and_threshold"],
-    "stil_ema_update": [f"{OPS}::test_ema_and_adam_slabs"],
+    "stil_onehot_argmax": [f"{OPS}::test_onehot_argmax_first_maximum_and_threshold", f"{KE}::test_onehot_argmax_beyond_one_wave", f"{KE}::test_onehot_argmax_ties_across_and_within_lanes_and_at_the_threshold"],
+    "stil_ema_update": [f"{OPS}::test_ema_and_adam_slabs", f"{KE}::test_ema_update_is_bit_exact_past_the_grid_cap", f"{KE}::test_ema_update_on_a_sub_slab"],
     "stil_ema_int_trunc": [f"{EP}::test_ema_int_trunc"],
-    "stil_adam_step": [f"{OPS}::test_ema_and_adam_slabs"],
+    "stil_adam_step": [f"{OPS}::test_ema_and_adam_slabs", f"{KE}::test_adam_five_steps_with_padding_and_a_lagging_tensor", f"{KE}::test_adam_slab_beyond_the_grid_cap"],
     "stil_metric_topk": [f"{EP}::test_metric_topk_on_a_column_slice_and_k_edges", f"{_MET}::test_topk_accuracy_counts"],
     "stil_metric_binary": [f"{EP}::test_metric_binary_at_the_threshold", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
     "stil_auroc_workspace_bytes": [f"{EP}::test_auroc_single_row_and_all_scores_equal"],
