@@ -36,3 +36,4 @@ extern "C" int stil_device_count(void) {
 #include "margent.hip"
 #include "deyo.hip"
 #include "sar.hip"
+#include "read.hip"

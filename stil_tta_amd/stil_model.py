@@ -48,10 +48,12 @@ _DEFAULTS = dict(
     tta_method=None,     # None (the shipped configs: test_step as the reference) | "tent" (Wang et al., ICLR 2021) | "eata" (Niu et al., ICML 2022)
                          # | "shot_im" (Liang et al., ICML 2020: entropy plus a batch-diversity term) | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
                          # | "marginal_entropy" (MEMO, Zhang et al., NeurIPS 2022: adapts on augmented views of each sample, scores the clean batch after the update)
+                         # | "read" (Yang et al., ICLR 2024: the encoders frozen, the fusion attention's Q/K/V projection adapted; needs tta_params "fusion")
                          # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
     tta_params="bn",     # "bn": BatchNorm affines of encoder_imaging | "norm": + LayerNorm affines of encoder_tabular / transformer
+                         # | "fusion": weight and bias of transformer[-1].attn.qkv alone, with "read" and only with it
     tta_bn_prior=None,   # N >= 0: the adapting forwards normalise by N/(N+B) source + B/(N+B) batch statistics (Schneider et al., NeurIPS 2020);
                          # None: the batch statistics alone
     # "eata" only: sample selection and the Fisher anchor
@@ -84,6 +86,10 @@ _DEFAULTS = dict(
                                    # CVPR 2023, alpha = 0.05) and one forward per batch updates it.  None: no estimate is kept.  "dua" (Mirza et al., CVPR 2022) needs it
     tta_bn_momentum_decay=1.0,     # omega and alpha_min of DUA's schedule: the t-th update (t = 1, 2, ...) uses alpha_t = min(1, alpha omega^t + alpha_min);
     tta_bn_momentum_min=0.0,       # DUA as published (values as recalled: unpinned): batches of 1, tta_views 64, 0.1 / 0.94 / 0.005
+    # "read" only: READ (Yang et al., ICLR 2024), the confidence-aware loss mean_r c_r log(e gamma / c_r) on the confidence c_r of every row plus
+    # tta_div_weight x the batch-balance term of "shot_im" (tta_div_eps inside its logarithm; 0 switches it off).  Form and defaults as recalled: unpinned
+    tta_read_gamma=None,           # gamma in (0, 1]: rows above it are pushed, rows below it damped; None = exp(-1), where the row loss is -c ln c.
+                                   # READ's published Adam rate is 1e-4 (as recalled: unpinned); tta_lr keeps its own default.  tta_bn_prior / tta_bn_momentum are refused
 )
 
 
@@ -670,7 +676,9 @@ class STiLModel(_Base):
         source values when the running mean of the loss falls below tta_sar_reset; the scores are the first pass's.
         With "dua" (tta.dua_step) the running estimate of the BatchNorm statistics takes one update from tta_views augmented views
         of the batch and the clean batch is then scored in eval mode on that estimate: forward only, nothing else is adapted.
-        With tta_bn_momentum every method normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
+        With "read" (tta.read_step) the encoders run as here, in eval mode under no_grad, and only the last fusion layer's Q/K/V
+        projection adapts (tta_params "fusion"); the scores are those of that forward, before the update.
+        With tta_bn_momentum every method but "read" normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)
         with torch.no_grad():

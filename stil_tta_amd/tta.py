@@ -1,10 +1,11 @@
 """Test-time adaptation in STiLModel.test_step (the TODO of STiLModel.py:523-524): TENT (Wang et al., ICLR 2021), EATA (Niu et
 al., ICML 2022), SHOT-IM (Liang et al., ICML 2020), MEMO's marginal entropy over augmented views (Zhang et al., NeurIPS 2022),
 DeYO's entropy-and-PLPD selection on a patch-shuffled second view (Lee et al., ICLR 2024), SAR's sharpness-aware two-pass
-entropy steps with model recovery (Niu et al., ICLR 2023) and the forward-only "bn_adapt" baseline, optionally under a
-source-statistics BatchNorm prior (tta_bn_prior).
+entropy steps with model recovery (Niu et al., ICLR 2023), READ's confidence-aware adaptation of the fusion attention with the
+encoders frozen (Yang et al., ICLR 2024) and the forward-only "bn_adapt" baseline, optionally under a source-statistics BatchNorm
+prior (tta_bn_prior).
 
-Every method but SAR is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
+Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its own loss and whatever follows the backward:
     tent_step              entropy           -> Adam over A
     eata_step              eata_entropy      -> Fisher anchor (when an estimate is loaded) -> Adam over A gated by n > 0
     shot_im_step           infomax           -> Adam over A
@@ -14,6 +15,8 @@ Every method but SAR is ONE adapting pass (`adapting_pass`) with its own loss an
                            clean batch -> Adam over A gated by n > 0
     sar_step               sar_entropy -> A + rho g / |g| -> sar_entropy again on the rows the first pass kept -> A restored ->
                            Adam over A gated by n > 0 -> recovery of A when the running mean of the loss falls below tta_sar_reset
+    read_step              its own pass (`fusion_pass`): the encoders in eval mode under no_grad, then the fusion layers and heads
+                           under grad with read_loss -> Adam over A = the last fusion layer's qkv weight and bias (tta_params "fusion")
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
     dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
@@ -40,7 +43,7 @@ from ._lib import lib
 from .flat import ALIGN, FlatState, _round_up
 from .ops import _chk, _p, _scale_by, _stream, join_side
 
-PARAMS = ("bn", "norm")
+PARAMS = ("bn", "norm", "fusion")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
 
 
@@ -90,6 +93,17 @@ def check_hparams(hp):
     for key, v in (("tta_bn_momentum", hp.tta_bn_momentum), ("tta_bn_momentum_decay", hp.tta_bn_momentum_decay), ("tta_bn_momentum_min", hp.tta_bn_momentum_min)):
         if v is not None and v > 1:
             raise ValueError(f"{key} must not exceed 1, not {v!r}")
+    _number(hp, "tta_read_gamma", 0, strict=True, also=(None,))
+    if hp.tta_read_gamma is not None and hp.tta_read_gamma > 1:
+        raise ValueError(f"tta_read_gamma must not exceed 1, not {hp.tta_read_gamma!r}")
+    if hp.tta_method == "read" and hp.tta_params != "fusion":
+        raise ValueError(f"tta_method 'read' adapts the fusion attention alone: set tta_params 'fusion' (this model: {hp.tta_params!r})")
+    if hp.tta_params == "fusion" and hp.tta_method != "read":
+        raise ValueError(f"tta_params 'fusion' is the adapted set of tta_method 'read' alone: set tta_method 'read' (this model: {hp.tta_method!r})")
+    if hp.tta_method == "read":
+        for key in ("tta_bn_prior", "tta_bn_momentum"):
+            if getattr(hp, key) is not None:
+                raise ValueError(f"tta_method 'read' keeps the encoders' normalisation at the source: {key} must be None, not {getattr(hp, key)!r}")
     if hp.tta_method == "dua" and hp.tta_bn_momentum is None:
         raise ValueError("tta_method 'dua' adapts the running estimate of the BatchNorm statistics alone: set tta_bn_momentum (DUA: 0.1)")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
@@ -102,7 +116,11 @@ def enabled(hp) -> bool:
 
 def param_names(model) -> List[str]:
     """The adapted set A, as state_dict names: weight and bias of every BatchNorm2d of model.encoder_imaging (downsample
-    BNs included); with tta_params == "norm" also of every LayerNorm of model.encoder_tabular and model.transformer."""
+    BNs included); with tta_params == "norm" also of every LayerNorm of model.encoder_tabular and model.transformer.
+    With tta_params == "fusion" (READ): weight and bias of the Q/K/V projection of the LAST fusion layer, nothing else."""
+    if model.hp.tta_params == "fusion":
+        last = len(model.model.transformer) - 1
+        return [f"model.transformer.{last}.attn.qkv.weight", f"model.transformer.{last}.attn.qkv.bias"]
     groups = [("model.encoder_imaging", model.model.encoder_imaging, nn.BatchNorm2d)]
     if model.hp.tta_params == "norm":
         groups += [("model.encoder_tabular", model.model.encoder_tabular, nn.LayerNorm), ("model.transformer", model.model.transformer, nn.LayerNorm)]
@@ -116,7 +134,7 @@ def param_names(model) -> List[str]:
 
 # ---------------------------------------------------------------------------------------------- losses
 class _RowLossFn(torch.autograd.Function):
-    """The one autograd node of the six losses below: launch(z) -> (loss, probabilities or None, dZ) makes the loss's single
+    """The one autograd node of the seven losses below: launch(z) -> (loss, probabilities or None, dZ) makes the loss's single
     library call, which forms dZ in the same launch sequence; the probabilities carry no gradient and backward scales dZ by the
     incoming gradient."""
 
@@ -293,6 +311,38 @@ def infomax(z, div_weight=1.0, eps=1e-5):
         lib().infomax_rows(_p(z), K, R, K, 1.0 / R, float(div_weight), float(eps), _p(lse), _p(p), K, _p(h), _p(pbar), _p(dz), K,
                            _p(out), _p(ws), _stream())
         info.update(loss_entropy=out[1], loss_diversity=out[2], marginal=pbar, H=h, lse=lse)
+        return out[0], p, dz
+
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
+
+
+def read_gamma(hp) -> float:
+    """tta_read_gamma resolved: None -> exp(-1), where the row loss is -c ln c"""
+    return math.exp(-1.0) if hp.tta_read_gamma is None else float(hp.tta_read_gamma)
+
+
+def read_loss(z, gamma=math.exp(-1.0), div_weight=1.0, eps=1e-5):
+    """READ's loss (Yang et al., ICLR 2024; form and constants as recalled: unpinned) beside infomax: the mean over rows of
+    f_r = c_r log(e gamma / c_r), c_r = softmax(z_r)[yhat_r] the confidence and yhat_r the first maximum of z_r, plus
+    div_weight x D, infomax's batch-balance term.  df/dc = ln(gamma / c): minimising f raises the confidence of the rows above
+    gamma and lowers that of the rows below (the noisy ones); gamma = 1/e gives f = -c ln c.  stil_read_rows forms lse, p, yhat,
+    c, f, pbar, D and dZ / rows (yhat held fixed); pbar and D are stil_infomax_rows' bit for bit.
+    -> (mean f + div_weight x D [autograd], softmax(z) [no grad], info);
+    info = dict(loss_confidence, loss_balance, marginal [K], yhat [int32], conf, f, lse), all on the device."""
+    info = {}
+
+    def launch(z):
+        _chk(z)
+        R, K = z.shape
+        lse, pbar = _empty(z, R, torch.float64), _empty(z, K, torch.float32)
+        conf, f = _empty(z, R, torch.float32, 2)
+        yhat = _empty(z, R, torch.int32)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        out = _empty(z, 3, torch.float32)
+        ws = _empty(z, 2 * K, torch.float64)
+        lib().read_rows(_p(z), K, R, K, 1.0 / R, float(gamma), float(div_weight), float(eps), _p(lse), _p(p), K, _p(yhat), _p(conf),
+                        _p(f), _p(pbar), _p(dz), K, _p(out), _p(ws), _stream())
+        info.update(loss_confidence=out[1], loss_balance=out[2], marginal=pbar, yhat=yhat, conf=conf, f=f, lse=lse)
         return out[0], p, dz
 
     return _RowLossFn.apply(z.contiguous(), launch) + (info,)
@@ -996,6 +1046,49 @@ def sar_step(model, batch):
         return model._score_test(probs, y)
 
 
+def fusion_pass(model, x, st, loss_fn):
+    """READ's pass on the inputs x = (images, table, ...) of a batch, not `adapting_pass`: (1) under no_grad, encoder_imaging in
+    eval mode on the checkpoint's running statistics and the tabular encoder, the launches plain test_step makes; (2) under grad,
+    forward_all(train=False) on those tokens: only A (the last fusion layer's qkv weight and bias) requires grad, so autograd
+    records nothing before that layer's qkv product and the backward never enters an encoder or an earlier fusion layer;
+    (3) loss_fn(out_m) -> (loss, probs, extras) and its backward, the two gradients into st.grads (one weight-gradient product
+    and one column sum).  Writes st.grads and whatever loss_fn writes; never a parameter, BatchNorm buffer, teacher, prototype or
+    training slab.  The caller holds torch.inference_mode(False).  -> (out_m, loss, probs, extras), detached."""
+    x_img, x_tab = _inputs(model, x)
+    net = model.model
+    with _grads_of(model, st):
+        with torch.no_grad():
+            x_i = net.encoder_imaging.run(x_img, False, None)
+            x_t = net.tabular_tokens(x_tab, False)
+        out_m = net.forward_all((x_img, x_tab), train=False, x_i=x_i, x_t=x_t)[0]
+        loss, probs, extras = loss_fn(out_m)
+        loss.backward()
+    return out_m.detach(), loss.detach(), probs, extras
+
+
+def read_step(model, batch):
+    """READ (Yang et al., ICLR 2024, "Test-time Adaptation against Multi-modal Reliability Bias"; form and constants as recalled:
+    unpinned) on one test batch: the modality encoders and their normalisation stay at the source (eval-mode BatchNorm on the
+    checkpoint's statistics, no gradient), A = the Q/K/V projection of the last fusion layer (tta_params "fusion"), the loss
+    read_loss = mean_r c_r log(e gamma / c_r) + tta_div_weight x sum_k pbar_k log(pbar_k + tta_div_eps) with gamma = tta_read_gamma
+    (None: 1/e), one Adam step over A (tta_lr; READ's published rate is 1e-4, as recalled).  The first method whose backward never
+    enters the ResNet (`fusion_pass`).  Writes A, its own moments and step counts, acc_test / auc_test and last_tta; never the
+    training slabs, buffers, teacher or prototypes.  The scores are softmax(out_m) of this forward, before the update: on the
+    first batch those of test_step without adaptation.  tta_bn_prior and tta_bn_momentum are refused with this method.  State,
+    Adam, episodic mode and reset are tent_step's.  Rank-local: no collectives.
+    last_tta: loss, loss_confidence, loss_balance, y_hat_m, probs, yhat, conf, marginal, all on the device: the step reads nothing
+    back."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        out_m, loss, probs, info = fusion_pass(model, x, st, lambda z: read_loss(z, read_gamma(hp), hp.tta_div_weight, hp.tta_div_eps))
+        st.adam_step(hp.tta_lr)
+        model.last_tta = dict(loss=loss, loss_confidence=info["loss_confidence"], loss_balance=info["loss_balance"], y_hat_m=out_m,
+                              probs=probs, yhat=info["yhat"], conf=info["conf"], marginal=info["marginal"])
+        return model._score_test(probs, y)
+
+
 def bn_adapt_step(model, batch):
     """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
     statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
@@ -1047,7 +1140,8 @@ def dua_step(model, batch):
 
 
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
-         "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step}   # tta_method -> STiLModel.test_step's body
+         "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step,
+         "read": read_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
