@@ -1,6 +1,9 @@
 // NHWC BatchNorm (train statistics / apply / backward), eval-mode affine folding, 3x3-s2 max-pool
 // and the stem im2col.  HBM-bound kernels: 16-byte coalesced accesses along the channel axis,
 // per-thread register accumulation, LDS cross-row reduction, fixed-order (deterministic) finals.
+// BatchNorm comes in three families (training here, the source-statistics prior in bn_prior.hip, the BatchNorm memory in
+// bn_memory.hip) that share every kernel and every launch sequence of this file and differ in a FINISH: what the last thread of a
+// channel makes of the reduced sums (see "the short kernels that FINISH a reduction" below).
 // Replaces nn.BatchNorm2d / nn.ReLU / residual add / nn.MaxPool2d of models/resnets.py:112-132,248-252.
 #include "common.h"
 
@@ -66,45 +69,45 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
   }
 }
 
-// stats[0]=mean, [1]=rstd, [2]=a=gamma*rstd, [3]=beta ; updates running stats (momentum, unbiased var)
-__global__ __launch_bounds__(256) void bn_stats_final_kernel(const float* __restrict__ Kp, const float* __restrict__ part, int nch, int M, int C,
-                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                      float* __restrict__ rmean, float* __restrict__ rvar, long long* nbt,
-                                      float* __restrict__ stats, float eps, float momentum) {
+// ---- the short kernels that FINISH a reduction.  Each is a SKELETON, written once and templated on a FINISH: the skeleton adds the
+// partials of channel c in a fixed order (deterministic) and the one thread that owns c hands the totals to the finish, a small
+// struct of pointers and scalars (a kernel argument) that states what this BatchNorm family makes of them:
+//   forward    fin.chunk(c, C, M, K[c], s1, s2)   pilot-shifted float sums of the two-pass path
+//              fin.tiles(c, C, M, s1, s2, s3)     double sums over the per-tile partials
+//   backward   fin(c, C, M, s1, s2)               sum g, sum g xhat as floats
+// The families: training (BnTrainFwd / BnTrainBwd below), the source-statistics prior and the BatchNorm memory (bn_prior.hip).
+template <class Finish>
+__global__ __launch_bounds__(256) void bn_fwd_final_kernel(const float* __restrict__ Kp, const float* __restrict__ part, int nch, int M,
+                                                            int C, const Finish fin) {
   __shared__ float sh[2 * 8 * 32];
-  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
   int c;
   float tot[2];
   if (!chunk_reduce<8, 2>(part, nch, C, sh, c, tot)) return;
-  const float s1 = tot[0], s2 = tot[1];
-  const float invM = 1.f / (float)M;
-  const float d = s1 * invM;
-  const float mean = Kp[c] + d;
-  float var = s2 * invM - d * d;
-  var = fmaxf(var, 0.f);
-  const float rstd = 1.f / sqrtf(var + eps);
-  const float a = gamma[c] * rstd;
-  stats[c] = mean; stats[C + c] = rstd; stats[2 * C + c] = a; stats[3 * C + c] = beta[c];
-  if (rmean) {
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-    float unb = (M > 1) ? var * ((float)M / (float)(M - 1)) : var;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
-  }
+  fin.chunk(c, C, M, Kp[c], tot[0], tot[1]);
 }
 
-// Same outputs from the per-tile (mean_t, M2_t) partials the conv GEMM's epilogue wrote (stil_gemm_nt colstats).
+// batch mean and (biased, clamped) variance from the pilot-shifted sums, in float
+__device__ __forceinline__ void bn_chunk_moments(float K, float s1, float s2, int M, float& mean, float& var) {
+  const float invM = 1.f / (float)M;
+  const float d = s1 * invM;
+  mean = K + d;
+  var = s2 * invM - d * d;
+  var = fmaxf(var, 0.f);
+}
+
+// Statistics from the per-tile (mean_t, M2_t) partials the conv GEMM's epilogue wrote (stil_gemm_nt colstats).
 // With n_t rows in tile t:  mean = S1/M,  M2 = S3 + (S2 - S1^2/M),  S1 = sum n_t mean_t, S2 = sum n_t mean_t^2, S3 = sum M2_t.
 // The three sums run in DOUBLE (every term is an exact product of floats, so the S2 - S1^2/M cancellation costs nothing),
 // split over `nsplit` blocks per 32 columns (stage 1) and added in a fixed order (stage 2): deterministic.
-// 256-thread workgroups (8 row lanes x 32 columns): these short dependent kernels run while the other stream's GEMM keeps
+// 256-thread workgroups (8 tile lanes x 32 columns): these short dependent kernels run while the other stream's GEMM keeps
 // every CU full of 256-thread workgroups -- a 1024-thread workgroup had to wait for four of them to retire on ONE CU
 // (55 us instead of 8 us per launch under the two-stream step).
-__global__ __launch_bounds__(256) void bn_tiles_stage1_kernel(const float* __restrict__ ts, int nt, int tile_rows, int M, int C,
-                                                                int tiles_per_split, double* __restrict__ part) {
-  __shared__ double sh[3 * 8 * 32];
+// The tile loop: lane l adds tiles t0 + l, t0 + l + 8, ... < t1, the 8 lane sums are added in order.  sh: 3 * 8 * 32 doubles.
+// Returns true in the threads (lane 0) that hold the totals of column c.
+__device__ __forceinline__ bool bn_tile_sums3(const float* __restrict__ ts, int t0, int t1, int tile_rows, int M, int C, double* sh,
+                                              int& c, double& a, double& b, double& d) {
   const int cl = threadIdx.x & 31, lane = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  const int t0 = blockIdx.y * tiles_per_split, t1 = min(nt, t0 + tiles_per_split);
+  c = blockIdx.x * 32 + cl;
   double s1 = 0.0, s2 = 0.0, s3 = 0.0;
   if (c < C)
     for (int t = t0 + lane; t < t1; t += 8) {
@@ -114,75 +117,87 @@ __global__ __launch_bounds__(256) void bn_tiles_stage1_kernel(const float* __res
     }
   sh[lane * 32 + cl] = s1; sh[256 + lane * 32 + cl] = s2; sh[512 + lane * 32 + cl] = s3;
   __syncthreads();
-  if (lane != 0 || c >= C) return;
-  double a = 0.0, b = 0.0, d = 0.0;
+  if (lane != 0 || c >= C) return false;
+  a = 0.0; b = 0.0; d = 0.0;
   for (int l = 0; l < 8; ++l) { a += sh[l * 32 + cl]; b += sh[256 + l * 32 + cl]; d += sh[512 + l * 32 + cl]; }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void bn_tiles_stage1_kernel(const float* __restrict__ ts, int nt, int tile_rows, int M, int C,
+                                                                int tiles_per_split, double* __restrict__ part) {
+  __shared__ double sh[3 * 8 * 32];
+  const int t0 = blockIdx.y * tiles_per_split;
+  int c;
+  double a, b, d;
+  if (!bn_tile_sums3(ts, t0, min(nt, t0 + tiles_per_split), tile_rows, M, C, sh, c, a, b, d)) return;
   const int nsplit = gridDim.y;
   part[((long)0 * nsplit + blockIdx.y) * C + c] = a;
   part[((long)1 * nsplit + blockIdx.y) * C + c] = b;
   part[((long)2 * nsplit + blockIdx.y) * C + c] = d;
 }
 
-__global__ __launch_bounds__(256) void bn_tiles_stage2_kernel(const double* __restrict__ part, int nsplit, int M, int C,
-                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                      float* __restrict__ rmean, float* __restrict__ rvar, long long* nbt,
-                                      float* __restrict__ stats, float eps, float momentum) {
+template <class Finish>
+__global__ __launch_bounds__(256) void bn_tiles_stage2_kernel(const double* __restrict__ part, int nsplit, int M, int C, const Finish fin) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0 && nbt) *nbt += 1;
   if (c >= C) return;
   double s1 = 0.0, s2 = 0.0, s3 = 0.0;
   for (int k = 0; k < nsplit; ++k) {
     s1 += part[((long)0 * nsplit + k) * C + c]; s2 += part[((long)1 * nsplit + k) * C + c]; s3 += part[((long)2 * nsplit + k) * C + c];
   }
-  const double mean_d = s1 / (double)M;
-  double m2 = s3 + (s2 - s1 * mean_d);
-  const float mean = (float)mean_d;
-  const float var = fmaxf((float)(m2 / (double)M), 0.f);
-  const float rstd = 1.f / sqrtf(var + eps);
-  stats[c] = mean; stats[C + c] = rstd; stats[2 * C + c] = gamma[c] * rstd; stats[3 * C + c] = beta[c];
-  if (rmean) {
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-    const float unb = (M > 1) ? var * ((float)M / (float)(M - 1)) : var;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
-  }
+  fin.tiles(c, C, M, s1, s2, s3);
 }
 
 // Both stages in ONE launch when a single split covers every tile (nt <= 256: small per-GPU batches, where the step is bound by
 // its ~1300 dependent launches and not by bytes).  Same sums in the same order as stage 1 + stage 2 with nsplit = 1: identical bits.
+template <class Finish>
 __global__ __launch_bounds__(256) void bn_tiles_fused_kernel(const float* __restrict__ ts, int nt, int tile_rows, int M, int C,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              float* __restrict__ rmean, float* __restrict__ rvar, long long* nbt,
-                                                              float* __restrict__ stats, float eps, float momentum) {
+                                                              const Finish fin) {
   __shared__ double sh[3 * 8 * 32];
-  const int cl = threadIdx.x & 31, lane = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
-  double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  if (c < C)
-    for (int t = lane; t < nt; t += 8) {
-      const double n = (double)min(tile_rows, M - t * tile_rows);
-      const double m = (double)ts[((long)t * 2) * C + c];
-      s1 += n * m; s2 += n * m * m; s3 += (double)ts[((long)t * 2 + 1) * C + c];
-    }
-  sh[lane * 32 + cl] = s1; sh[256 + lane * 32 + cl] = s2; sh[512 + lane * 32 + cl] = s3;
-  __syncthreads();
-  if (lane != 0 || c >= C) return;
-  double a = 0.0, b = 0.0, d = 0.0;
-  for (int l = 0; l < 8; ++l) { a += sh[l * 32 + cl]; b += sh[256 + l * 32 + cl]; d += sh[512 + l * 32 + cl]; }
-  double t1 = 0.0, t2 = 0.0, t3 = 0.0;   // stage 2's loop over its one split
-  t1 += a; t2 += b; t3 += d;
-  const double mean_d = t1 / (double)M;
-  double m2 = t3 + (t2 - t1 * mean_d);
-  const float mean = (float)mean_d;
-  const float var = fmaxf((float)(m2 / (double)M), 0.f);
-  const float rstd = 1.f / sqrtf(var + eps);
-  stats[c] = mean; stats[C + c] = rstd; stats[2 * C + c] = gamma[c] * rstd; stats[3 * C + c] = beta[c];
-  if (rmean) {
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-    const float unb = (M > 1) ? var * ((float)M / (float)(M - 1)) : var;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
-  }
+  int c;
+  double a, b, d;
+  if (!bn_tile_sums3(ts, 0, nt, tile_rows, M, C, sh, c, a, b, d)) return;
+  fin.tiles(c, C, M, a, b, d);
 }
+
+// batch mean and M2 / M (biased variance before the clamp at zero) from the three tile sums, in double
+__device__ __forceinline__ void bn_tile_moments(double s1, double s2, double s3, int M, double& mean, double& var) {
+  mean = s1 / (double)M;
+  const double m2 = s3 + (s2 - s1 * mean);
+  var = m2 / (double)M;
+}
+
+// Training: stats[0]=mean, [1]=rstd, [2]=a=gamma*rstd, [3]=beta; updates the running statistics (momentum, unbiased variance) and
+// counts the batch (the thread that owns channel 0: once per launch), each unless its pointer is NULL.  Float arithmetic throughout.
+struct BnTrainFwd {
+  const float *gamma, *beta;
+  float *rmean, *rvar;
+  long long* nbt;
+  float* stats;
+  float eps, momentum;
+  __device__ __forceinline__ void write(int c, int C, int M, float mean, float var) const {
+    // every load ahead of the first store: the members carry no __restrict__, so a load behind a store would wait its turn
+    const float g = gamma[c], b = beta[c], rm = rmean ? rmean[c] : 0.f, rv = rmean ? rvar[c] : 0.f;
+    if (c == 0 && nbt) *nbt += 1;
+    const float rstd = 1.f / sqrtf(var + eps);
+    const float a = g * rstd;
+    stats[c] = mean; stats[C + c] = rstd; stats[2 * C + c] = a; stats[3 * C + c] = b;
+    if (rmean) {
+      rmean[c] = (1.f - momentum) * rm + momentum * mean;
+      const float unb = (M > 1) ? var * ((float)M / (float)(M - 1)) : var;
+      rvar[c] = (1.f - momentum) * rv + momentum * unb;
+    }
+  }
+  __device__ __forceinline__ void chunk(int c, int C, int M, float K, float s1, float s2) const {
+    float mean, var;
+    bn_chunk_moments(K, s1, s2, M, mean, var);
+    write(c, C, M, mean, var);
+  }
+  __device__ __forceinline__ void tiles(int c, int C, int M, double s1, double s2, double s3) const {
+    double mean_d, var_d;
+    bn_tile_moments(s1, s2, s3, M, mean_d, var_d);
+    write(c, C, M, (float)mean_d, fmaxf((float)var_d, 0.f));
+  }
+};
 
 // eval mode: ab[0] = a = gamma / sqrt(running_var + eps), ab[1] = beta, ab[2] = running_mean.  The conv epilogue
 // applies (y - mean) * a + beta: the subtractive form keeps ATen's accuracy (no x*a - mean*a cancellation).
@@ -273,31 +288,21 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
   }
 }
 
-// dgamma/dbeta (+)= ; coef[0]=gamma*rstd, [1]=dbeta/M, [2]=dgamma/M
-__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ part, int nch, int M, int C,
-                                    const float* __restrict__ gamma, const float* __restrict__ stats,
-                                    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef,
-                                    int accumulate) {
+// ---- backward finals (skeletons as in the forward): the finish gets s1 = sum g, s2 = sum g xhat of channel c as floats
+template <class Finish>
+__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ part, int nch, int M, int C, const Finish fin) {
   __shared__ float sh[2 * 8 * 32];
   int c;
   float tot[2];
   if (!chunk_reduce<8, 2>(part, nch, C, sh, c, tot)) return;
-  const float s1 = tot[0], s2 = tot[1];
-  if (dbeta) dbeta[c] = accumulate ? dbeta[c] + s1 : s1;
-  if (dgamma) dgamma[c] = accumulate ? dgamma[c] + s2 : s2;
-  const float invM = 1.f / (float)M;
-  coef[c] = gamma[c] * stats[C + c];
-  coef[C + c] = s1 * invM;
-  coef[2 * C + c] = s2 * invM;
+  fin(c, C, M, tot[0], tot[1]);
 }
 
 // The same over 32 lanes x 8 column quads per workgroup (C % 4 == 0): one dwordx4 per lane and chunk, a dependent chain of
 // nch / 32 loads instead of nch / 8 (the kernel is that chain: 25 us alone, 110-160 us beside the other stream's GEMMs, on
 // the main stream of every BatchNorm backward).  Lane sums are added in lane order: deterministic.
-__global__ __launch_bounds__(256) void bn_bwd_final4_kernel(const float* __restrict__ part, int nch, int M, int C,
-                                     const float* __restrict__ gamma, const float* __restrict__ stats,
-                                     float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef,
-                                     int accumulate) {
+template <class Finish>
+__global__ __launch_bounds__(256) void bn_bwd_final4_kernel(const float* __restrict__ part, int nch, int M, int C, const Finish fin) {
   __shared__ float4 sh[2 * 32 * 8];
   const int cq = threadIdx.x & 7, lane = threadIdx.x >> 3;
   const int c = (blockIdx.x * 8 + cq) * 4;
@@ -318,28 +323,19 @@ __global__ __launch_bounds__(256) void bn_bwd_final4_kernel(const float* __restr
     b.x += v.x; b.y += v.y; b.z += v.z; b.w += v.w;
   }
   const float s1[4] = {a.x, a.y, a.z, a.w}, s2[4] = {b.x, b.y, b.z, b.w};
-  const float invM = 1.f / (float)M;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int cc = c + j;
-    if (dbeta) dbeta[cc] = accumulate ? dbeta[cc] + s1[j] : s1[j];
-    if (dgamma) dgamma[cc] = accumulate ? dgamma[cc] + s2[j] : s2[j];
-    coef[cc] = gamma[cc] * stats[C + cc];
-    coef[C + cc] = s1[j] * invM;
-    coef[2 * C + cc] = s2[j] * invM;
-  }
+  for (int j = 0; j < 4; ++j) fin(c + j, C, M, s1[j], s2[j]);
 }
 
 // ---- backward statistics from per-tile partials: the input-gradient GEMM that PRODUCED dz left, per 64-row tile t and column,
 // ts[(2t)*C + c] = sum g', ts[(2t+1)*C + c] = sum g' * xhat (stil_gemm_nt `bstats`), so no pass over dz and x is needed.  Two short
 // kernels combine them in DOUBLE in a fixed order (stage 1: nsplit blocks per 32 columns, 8 tile lanes each; final: the
-// nsplit sums), then write what bn_bwd_final_kernel writes.
-__global__ __launch_bounds__(256) void bn_bwd_tiles_stage1_kernel(const float* __restrict__ ts, int nt, int C, int tiles_per_split,
-                                                                   double* __restrict__ part) {
-  __shared__ double sh[2 * 8 * 32];
+// nsplit sums, rounded to float for the finish), or one kernel when a single split covers every tile: identical bits.
+// The tile loop, as bn_tile_sums3.  sh: 2 * 8 * 32 doubles.
+__device__ __forceinline__ bool bn_tile_sums2(const float* __restrict__ ts, int t0, int t1, int C, double* sh, int& c, double& a,
+                                              double& b) {
   const int cl = threadIdx.x & 31, lane = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  const int t0 = blockIdx.y * tiles_per_split, t1 = min(nt, t0 + tiles_per_split);
+  c = blockIdx.x * 32 + cl;
   double s1 = 0.0, s2 = 0.0;
   if (c < C)
     for (int t = t0 + lane; t < t1; t += 8) {
@@ -348,59 +344,60 @@ __global__ __launch_bounds__(256) void bn_bwd_tiles_stage1_kernel(const float* _
     }
   sh[lane * 32 + cl] = s1; sh[256 + lane * 32 + cl] = s2;
   __syncthreads();
-  if (lane != 0 || c >= C) return;
-  double a = 0.0, b = 0.0;
+  if (lane != 0 || c >= C) return false;
+  a = 0.0; b = 0.0;
   for (int l = 0; l < 8; ++l) { a += sh[l * 32 + cl]; b += sh[256 + l * 32 + cl]; }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_tiles_stage1_kernel(const float* __restrict__ ts, int nt, int C, int tiles_per_split,
+                                                                   double* __restrict__ part) {
+  __shared__ double sh[2 * 8 * 32];
+  const int t0 = blockIdx.y * tiles_per_split;
+  int c;
+  double a, b;
+  if (!bn_tile_sums2(ts, t0, min(nt, t0 + tiles_per_split), C, sh, c, a, b)) return;
   const int nsplit = gridDim.y;
   part[((long)0 * nsplit + blockIdx.y) * C + c] = a;
   part[((long)1 * nsplit + blockIdx.y) * C + c] = b;
 }
+
+template <class Finish>
 __global__ __launch_bounds__(256) void bn_bwd_tiles_final_kernel(const double* __restrict__ part, int nsplit, int M, int C,
-                                                                  const float* __restrict__ gamma, const float* __restrict__ stats,
-                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                  float* __restrict__ coef, int accumulate) {
+                                                                  const Finish fin) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   double a = 0.0, b = 0.0;
   for (int k = 0; k < nsplit; ++k) { a += part[((long)0 * nsplit + k) * C + c]; b += part[((long)1 * nsplit + k) * C + c]; }
-  const float s1 = (float)a, s2 = (float)b;
-  if (dbeta) dbeta[c] = accumulate ? dbeta[c] + s1 : s1;
-  if (dgamma) dgamma[c] = accumulate ? dgamma[c] + s2 : s2;
-  const float invM = 1.f / (float)M;
-  coef[c] = gamma[c] * stats[C + c];
-  coef[C + c] = s1 * invM;
-  coef[2 * C + c] = s2 * invM;
+  fin(c, C, M, (float)a, (float)b);
 }
 
-// ... and in one launch when a single split covers every tile (see bn_tiles_fused_kernel): identical bits.
-__global__ __launch_bounds__(256) void bn_bwd_tiles_fused_kernel(const float* __restrict__ ts, int nt, int M, int C,
-                                                                  const float* __restrict__ gamma, const float* __restrict__ stats,
-                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                  float* __restrict__ coef, int accumulate) {
+template <class Finish>
+__global__ __launch_bounds__(256) void bn_bwd_tiles_fused_kernel(const float* __restrict__ ts, int nt, int M, int C, const Finish fin) {
   __shared__ double sh[2 * 8 * 32];
-  const int cl = threadIdx.x & 31, lane = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int t = lane; t < nt; t += 8) {
-      s1 += (double)ts[((long)t * 2) * C + c];
-      s2 += (double)ts[((long)t * 2 + 1) * C + c];
-    }
-  sh[lane * 32 + cl] = s1; sh[256 + lane * 32 + cl] = s2;
-  __syncthreads();
-  if (lane != 0 || c >= C) return;
-  double a = 0.0, b = 0.0;
-  for (int l = 0; l < 8; ++l) { a += sh[l * 32 + cl]; b += sh[256 + l * 32 + cl]; }
-  double ta = 0.0, tb = 0.0;
-  ta += a; tb += b;
-  const float f1 = (float)ta, f2 = (float)tb;
-  if (dbeta) dbeta[c] = accumulate ? dbeta[c] + f1 : f1;
-  if (dgamma) dgamma[c] = accumulate ? dgamma[c] + f2 : f2;
-  const float invM = 1.f / (float)M;
-  coef[c] = gamma[c] * stats[C + c];
-  coef[C + c] = f1 * invM;
-  coef[2 * C + c] = f2 * invM;
+  int c;
+  double a, b;
+  if (!bn_tile_sums2(ts, 0, nt, C, sh, c, a, b)) return;
+  fin(c, C, M, (float)a, (float)b);
 }
+
+// Training: dgamma / dbeta (+)= ; coef[0] = gamma*rstd, [1] = dbeta/M, [2] = dgamma/M
+struct BnTrainBwd {
+  const float *gamma, *stats;
+  float *dgamma, *dbeta, *coef;
+  int accumulate;
+  __device__ __forceinline__ void operator()(int c, int C, int M, float s1, float s2) const {
+    // every load ahead of the first store (see BnTrainFwd::write)
+    const float g = gamma[c], rstd = stats[C + c];
+    const float b0 = (accumulate && dbeta) ? dbeta[c] : 0.f, g0 = (accumulate && dgamma) ? dgamma[c] : 0.f;
+    if (dbeta) dbeta[c] = accumulate ? b0 + s1 : s1;
+    if (dgamma) dgamma[c] = accumulate ? g0 + s2 : s2;
+    const float invM = 1.f / (float)M;
+    coef[c] = g * rstd;
+    coef[C + c] = s1 * invM;
+    coef[2 * C + c] = s2 * invM;
+  }
+};
 
 // dx = gamma*rstd * (g - dbeta/M - xhat*dgamma/M)
 __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict__ dz, const float* __restrict__ z,
@@ -565,30 +562,151 @@ extern "C" size_t stil_bn_workspace_bytes(int M, int C) {
   return ((size_t)2 * bn_chunks(M, C, ct) + 1) * C * sizeof(float);
 }
 
+static inline int bn_tiles_nsplit(int nt) { return cdiv(nt, 256); }
+extern "C" size_t stil_bn_tiles_workspace_bytes(int M, int C, int tile_rows) {
+  if (M <= 0 || C <= 0 || tile_rows <= 0) return 0;
+  return (size_t)3 * bn_tiles_nsplit(cdiv(M, tile_rows)) * C * sizeof(double);
+}
+extern "C" size_t stil_bn_bwd_tiles_workspace_bytes(int ntiles, int C) {
+  if (ntiles <= 0 || C <= 0) return 0;
+  return (size_t)2 * bn_tiles_nsplit(ntiles) * C * sizeof(double);
+}
+
+// grid of the wide element-wise passes (bn_apply_kernel, bn_bwd_dx_kernel): one float4 per thread and step
+static inline int bn_wide_grid(int M, int C, long* total4) {
+  *total4 = (long)M * C / 4;
+  const long blocks = (*total4 + 255) / 256;
+  return (int)(blocks < 8192 ? blocks : 8192);
+}
+
+// ---- the launch sequences, one per path, templated on the finish; `who` names the calling entry point in the messages.  Each checks
+// the shape and the workspace before its first launch.  What only one family refuses (its null pointers, rho, the memory's
+// arguments) the entry point checks before it comes here.
+// forward, statistics by two passes over x: pilot, partial sums, final, apply.  final_only: the final alone, over the partial sums an
+// earlier call of the same shape left in the workspace.
+template <class Finish>
+static int bn_fwd_two_pass(const char* who, const Finish& fin, const float* x, const float* resid, float* z, const float* stats, int M,
+                           int C, int relu, float* workspace, size_t workspace_bytes, hipStream_t s, bool final_only = false) {
+  const int ct = pick_ctile(C);
+  STIL_REQUIRE(ct != 0, "%s: C=%d must be a multiple of 64", who, C);
+  const int nch = bn_chunks(M, C, ct);
+  STIL_REQUIRE(workspace_bytes >= ((size_t)2 * nch + 1) * C * sizeof(float), "%s: workspace too small", who);
+  float* pilot = workspace + (size_t)2 * nch * C;
+  if (!final_only) {
+    hipLaunchKernelGGL(bn_pilot_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, x, pilot, M, C);
+    STIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C / ct, nch), dim3(256), 0, s, x, pilot, workspace, M, C, ct, cdiv(M, nch));
+    STIL_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(bn_fwd_final_kernel<Finish>, dim3(cdiv(C, 32)), dim3(256), 0, s, pilot, workspace, nch, M, C, fin);
+  STIL_LAUNCH_CHECK();
+  if (final_only) return STIL_OK;
+  long total4;
+  const int grid = bn_wide_grid(M, C, &total4);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, stats, resid, (const float*)nullptr, z, total4, C, relu);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+// forward, statistics from the per-tile partials of the producing GEMM (tilestats: [2*cdiv(M,tile_rows), C]): one launch, or
+// stage 1 + stage 2, then apply unless z == NULL (statistics only: the consumer applies them while it stages its operand).
+// final_only: the final alone (stage 1's sums are in the workspace already).
+template <class Finish>
+static int bn_fwd_tiles(const char* who, const Finish& fin, const float* x, const float* tilestats, int tile_rows, const float* resid,
+                        const float* resid_stats, float* z, const float* stats, int M, int C, int relu, void* workspace,
+                        size_t workspace_bytes, hipStream_t s, bool final_only = false) {
+  STIL_REQUIRE(z || !resid, "%s: statistics-only call (z == NULL) cannot take a residual", who);
+  STIL_REQUIRE(!resid_stats || resid, "%s: resid_stats without resid", who);
+  STIL_REQUIRE(tile_rows > 0 && M > 0 && C > 0 && C % 4 == 0, "%s: bad shape M=%d C=%d tile_rows=%d", who, M, C, tile_rows);
+  STIL_REQUIRE(workspace_bytes >= stil_bn_tiles_workspace_bytes(M, C, tile_rows) && ((uintptr_t)workspace % 8) == 0,
+               "%s: workspace too small or not 8-byte aligned", who);
+  const int nt = cdiv(M, tile_rows), nsplit = bn_tiles_nsplit(nt);
+  if (nsplit == 1) {   // one launch: every tile fits one split
+    hipLaunchKernelGGL(bn_tiles_fused_kernel<Finish>, dim3(cdiv(C, 32)), dim3(256), 0, s, tilestats, nt, tile_rows, M, C, fin);
+    STIL_LAUNCH_CHECK();
+  } else {
+    if (!final_only) {
+      hipLaunchKernelGGL(bn_tiles_stage1_kernel, dim3(cdiv(C, 32), nsplit), dim3(256), 0, s, tilestats, nt, tile_rows, M, C,
+                         cdiv(nt, nsplit), (double*)workspace);
+      STIL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(bn_tiles_stage2_kernel<Finish>, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, nsplit, M, C, fin);
+    STIL_LAUNCH_CHECK();
+  }
+  if (!z || final_only) return STIL_OK;
+  long total4;
+  const int grid = bn_wide_grid(M, C, &total4);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, stats, resid, resid_stats, z, total4, C, relu);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+// backward, sums by a pass over dz and x: partial sums (optionally storing g = dz * mask in gout), final, dx.
+// dz: grad wrt the block output; z: that output; x: conv output (pre-BN).  relu: 0 = none, 1 = mask from z (z > 0),
+// 2 = mask recomputed from x and the saved statistics (only valid without a residual input: saves reading z twice).
+template <class Finish>
+static int bn_bwd_two_pass(const char* who, const Finish& fin, const float* dz, const float* z, const float* x, const float* stats,
+                           const float* coef, float* dx, float* gout, int M, int C, int relu, float* workspace, size_t workspace_bytes,
+                           hipStream_t s) {
+  STIL_REQUIRE(relu >= 0 && relu <= 2 && (relu != 1 || z), "%s: relu must be 0, 1 (needs z) or 2", who);
+  const int ct = pick_ctile(C);
+  STIL_REQUIRE(ct != 0, "%s: C=%d must be a multiple of 64", who, C);
+  const int nch = bn_chunks(M, C, ct);
+  STIL_REQUIRE(workspace_bytes >= (size_t)2 * nch * C * sizeof(float), "%s: workspace too small", who);
+  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(C / ct, nch), dim3(256), 0, s, dz, z, x, stats, gout, workspace, M, C, ct,
+                     cdiv(M, nch), relu);
+  STIL_LAUNCH_CHECK();
+  if (((uintptr_t)workspace % 16) == 0)   // float4 loads: C % 64 == 0 here
+    hipLaunchKernelGGL(bn_bwd_final4_kernel<Finish>, dim3(cdiv(C, 32)), dim3(256), 0, s, workspace, nch, M, C, fin);
+  else
+    hipLaunchKernelGGL(bn_bwd_final_kernel<Finish>, dim3(cdiv(C, 32)), dim3(256), 0, s, workspace, nch, M, C, fin);
+  STIL_LAUNCH_CHECK();
+  long total4;
+  const int grid = bn_wide_grid(M, C, &total4);
+  // if g was materialised, read it (already masked) instead of dz,z
+  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid), dim3(256), 0, s, gout ? gout : dz, z, x, stats, coef, dx, total4, C, gout ? 0 : relu);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+// backward when the GEMM that produced dz already left the per-tile sums (stil_gemm_nt `bstats`): statistics from `tilestats`
+// [2*ntiles][C] (one launch, or stage 1 + final), then the dx pass.  relu as above (the mask the sums were formed with: 0 = dz is
+// final, 2 = recomputed from x and the statistics; 1 = from z).
+template <class Finish>
+static int bn_bwd_tiles(const char* who, const Finish& fin, const float* dz, const float* z, const float* x, const float* stats,
+                        const float* tilestats, int ntiles, const float* coef, float* dx, int M, int C, int relu, void* workspace,
+                        size_t workspace_bytes, hipStream_t s) {
+  STIL_REQUIRE(relu >= 0 && relu <= 2 && (relu != 1 || z), "%s: relu must be 0, 1 (needs z) or 2", who);
+  STIL_REQUIRE(ntiles > 0 && M > 0 && C > 0 && C % 4 == 0, "%s: bad shape M=%d C=%d ntiles=%d", who, M, C, ntiles);
+  STIL_REQUIRE(workspace_bytes >= stil_bn_bwd_tiles_workspace_bytes(ntiles, C) && ((uintptr_t)workspace % 8) == 0,
+               "%s: workspace too small or not 8-byte aligned", who);
+  const int nsplit = bn_tiles_nsplit(ntiles);
+  if (nsplit == 1) {
+    hipLaunchKernelGGL(bn_bwd_tiles_fused_kernel<Finish>, dim3(cdiv(C, 32)), dim3(256), 0, s, tilestats, ntiles, M, C, fin);
+    STIL_LAUNCH_CHECK();
+  } else {
+    hipLaunchKernelGGL(bn_bwd_tiles_stage1_kernel, dim3(cdiv(C, 32), nsplit), dim3(256), 0, s, tilestats, ntiles, C, cdiv(ntiles, nsplit),
+                       (double*)workspace);
+    STIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_tiles_final_kernel<Finish>, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, nsplit, M, C, fin);
+    STIL_LAUNCH_CHECK();
+  }
+  long total4;
+  const int grid = bn_wide_grid(M, C, &total4);
+  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid), dim3(256), 0, s, dz, z, x, stats, coef, dx, total4, C, relu);
+  STIL_LAUNCH_CHECK();
+  return STIL_OK;
+}
+
+// ---- the training entry points
+// M > 0 is not checked here (the prior and the memory check it): a call with M <= 0 launches over no rows, as it always has.
 extern "C" int stil_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean,
                                  float* running_var, long long* num_batches_tracked, const float* resid, float* z,
                                  float* stats, int M, int C, int relu, float eps, float momentum, float* workspace,
                                  size_t workspace_bytes, void* stream) {
   STIL_REQUIRE(x && gamma && beta && z && stats && workspace, "stil_bn_train_fwd: null pointer");
-  int ct = pick_ctile(C);
-  STIL_REQUIRE(ct != 0, "stil_bn_train_fwd: C=%d must be a multiple of 64", C);
-  int nch = bn_chunks(M, C, ct);
-  STIL_REQUIRE(workspace_bytes >= ((size_t)2 * nch + 1) * C * sizeof(float), "stil_bn_train_fwd: workspace too small");
-  float* pilot = workspace + (size_t)2 * nch * C;
-  int rpc = cdiv(M, nch);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_pilot_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, x, pilot, M, C);
-  STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C / ct, nch), dim3(256), 0, s, x, pilot, workspace, M, C, ct, rpc);
-  STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, pilot, workspace, nch, M, C, gamma, beta,
-                     running_mean, running_var, num_batches_tracked, stats, eps, momentum);
-  STIL_LAUNCH_CHECK();
-  long total4 = (long)M * C / 4;
-  int grid = (int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, stats, resid, (const float*)nullptr, z, total4, C, relu);
-  STIL_LAUNCH_CHECK();
-  return STIL_OK;
+  const BnTrainFwd fin{gamma, beta, running_mean, running_var, num_batches_tracked, stats, eps, momentum};
+  return bn_fwd_two_pass("stil_bn_train_fwd", fin, x, resid, z, stats, M, C, relu, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int stil_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
@@ -600,113 +718,35 @@ extern "C" int stil_bn_eval_affine(const float* gamma, const float* beta, const 
   return STIL_OK;
 }
 
-// Training forward when the producing GEMM already wrote per-tile statistics (tilestats: [2*cdiv(M,tile_rows), C]).
-static inline int bn_tiles_nsplit(int nt) { return cdiv(nt, 256); }
-extern "C" size_t stil_bn_tiles_workspace_bytes(int M, int C, int tile_rows) {
-  if (M <= 0 || C <= 0 || tile_rows <= 0) return 0;
-  return (size_t)3 * bn_tiles_nsplit(cdiv(M, tile_rows)) * C * sizeof(double);
-}
+// Training forward when the producing GEMM already wrote per-tile statistics.
 extern "C" int stil_bn_train_fwd_tiles(const float* x, const float* tilestats, int tile_rows, const float* gamma, const float* beta,
                                        float* running_mean, float* running_var, long long* num_batches_tracked,
                                        const float* resid, const float* resid_stats, float* z, float* stats, int M, int C, int relu,
                                        float eps, float momentum, void* workspace, size_t workspace_bytes, void* stream) {
   STIL_REQUIRE(x && tilestats && gamma && beta && stats && workspace, "stil_bn_train_fwd_tiles: null pointer");
-  STIL_REQUIRE(z || !resid, "stil_bn_train_fwd_tiles: statistics-only call (z == NULL) cannot take a residual");
-  STIL_REQUIRE(tile_rows > 0 && M > 0 && C % 4 == 0, "stil_bn_train_fwd_tiles: bad shape M=%d C=%d tile_rows=%d", M, C, tile_rows);
-  STIL_REQUIRE(workspace_bytes >= stil_bn_tiles_workspace_bytes(M, C, tile_rows) && ((uintptr_t)workspace % 8) == 0,
-               "stil_bn_train_fwd_tiles: workspace too small or not 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int nt = cdiv(M, tile_rows), nsplit = bn_tiles_nsplit(nt);
-  if (nsplit == 1) {   // one launch: every tile fits one split
-    hipLaunchKernelGGL(bn_tiles_fused_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, tilestats, nt, tile_rows, M, C, gamma, beta,
-                       running_mean, running_var, num_batches_tracked, stats, eps, momentum);
-    STIL_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(bn_tiles_stage1_kernel, dim3(cdiv(C, 32), nsplit), dim3(256), 0, s, tilestats, nt, tile_rows, M, C,
-                       cdiv(nt, nsplit), (double*)workspace);
-    STIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_tiles_stage2_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, nsplit, M, C, gamma, beta,
-                       running_mean, running_var, num_batches_tracked, stats, eps, momentum);
-    STIL_LAUNCH_CHECK();
-  }
-  if (!z) return STIL_OK;   // statistics only: the consumer applies them while it stages its operand
-  long total4 = (long)M * C / 4;
-  int grid = (int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-  STIL_REQUIRE(!resid_stats || resid, "stil_bn_train_fwd_tiles: resid_stats without resid");
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, stats, resid, resid_stats, z, total4, C, relu);
-  STIL_LAUNCH_CHECK();
-  return STIL_OK;
+  const BnTrainFwd fin{gamma, beta, running_mean, running_var, num_batches_tracked, stats, eps, momentum};
+  return bn_fwd_tiles("stil_bn_train_fwd_tiles", fin, x, tilestats, tile_rows, resid, resid_stats, z, stats, M, C, relu, workspace,
+                      workspace_bytes, (hipStream_t)stream);
 }
 
-// dz: grad wrt the block output; z: that output; x: conv output (pre-BN).  relu: 0 = none, 1 = mask from z (z > 0),
-// 2 = mask recomputed from x and the saved statistics (only valid without a residual input: saves reading z twice).
 // gout (optional): receives g = dz*mask (the gradient of the residual branch).  coef: [3*C] scratch.
 extern "C" int stil_bn_train_bwd(const float* dz, const float* z, const float* x, const float* gamma,
                                  const float* stats, float* dx, float* gout, float* dgamma, float* dbeta, float* coef,
                                  int M, int C, int relu, int accumulate, float* workspace, size_t workspace_bytes,
                                  void* stream) {
   STIL_REQUIRE(dz && x && gamma && stats && dx && coef && workspace, "stil_bn_train_bwd: null pointer");
-  STIL_REQUIRE(relu >= 0 && relu <= 2 && (relu != 1 || z), "stil_bn_train_bwd: relu must be 0, 1 (needs z) or 2");
-  int ct = pick_ctile(C);
-  STIL_REQUIRE(ct != 0, "stil_bn_train_bwd: C=%d must be a multiple of 64", C);
-  int nch = bn_chunks(M, C, ct);
-  STIL_REQUIRE(workspace_bytes >= (size_t)2 * nch * C * sizeof(float), "stil_bn_train_bwd: workspace too small");
-  int rpc = cdiv(M, nch);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(C / ct, nch), dim3(256), 0, s, dz, z, x, stats, gout, workspace, M, C,
-                     ct, rpc, relu);
-  STIL_LAUNCH_CHECK();
-  if (C % 4 == 0 && ((uintptr_t)workspace % 16) == 0)
-    hipLaunchKernelGGL(bn_bwd_final4_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, workspace, nch, M, C, gamma, stats, dgamma,
-                       dbeta, coef, accumulate);
-  else
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, workspace, nch, M, C, gamma, stats, dgamma,
-                       dbeta, coef, accumulate);
-  STIL_LAUNCH_CHECK();
-  long total4 = (long)M * C / 4;
-  int grid = (int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-  // if g was materialised, read it (already masked) instead of dz,z
-  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid), dim3(256), 0, s, gout ? gout : dz, z, x, stats, coef, dx, total4, C,
-                     gout ? 0 : relu);
-  STIL_LAUNCH_CHECK();
-  return STIL_OK;
+  const BnTrainBwd fin{gamma, stats, dgamma, dbeta, coef, accumulate};
+  return bn_bwd_two_pass("stil_bn_train_bwd", fin, dz, z, x, stats, coef, dx, gout, M, C, relu, workspace, workspace_bytes,
+                         (hipStream_t)stream);
 }
 
-// BatchNorm backward when the GEMM that produced dz already left the per-tile sums (stil_gemm_nt `bstats`): statistics from
-// `tilestats` [2*ntiles][C] (two short kernels), then the dx pass of stil_bn_train_bwd.  relu as there (the mask the sums were
-// formed with: 0 = dz is final, 2 = recomputed from x and the statistics; 1 = from z).
-static inline int bn_bwd_tiles_nsplit(int nt) { return cdiv(nt, 256); }
-extern "C" size_t stil_bn_bwd_tiles_workspace_bytes(int ntiles, int C) {
-  if (ntiles <= 0 || C <= 0) return 0;
-  return (size_t)2 * bn_bwd_tiles_nsplit(ntiles) * C * sizeof(double);
-}
 extern "C" int stil_bn_train_bwd_tiles(const float* dz, const float* z, const float* x, const float* gamma, const float* stats,
                                        const float* tilestats, int ntiles, float* dx, float* dgamma, float* dbeta, float* coef,
                                        int M, int C, int relu, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
   STIL_REQUIRE(dz && x && gamma && stats && tilestats && dx && coef && workspace, "stil_bn_train_bwd_tiles: null pointer");
-  STIL_REQUIRE(relu >= 0 && relu <= 2 && (relu != 1 || z), "stil_bn_train_bwd_tiles: relu must be 0, 1 (needs z) or 2");
-  STIL_REQUIRE(ntiles > 0 && M > 0 && C % 4 == 0, "stil_bn_train_bwd_tiles: bad shape M=%d C=%d ntiles=%d", M, C, ntiles);
-  STIL_REQUIRE(workspace_bytes >= stil_bn_bwd_tiles_workspace_bytes(ntiles, C) && ((uintptr_t)workspace % 8) == 0,
-               "stil_bn_train_bwd_tiles: workspace too small or not 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int nsplit = bn_bwd_tiles_nsplit(ntiles);
-  if (nsplit == 1) {
-    hipLaunchKernelGGL(bn_bwd_tiles_fused_kernel, dim3(cdiv(C, 32)), dim3(256), 0, s, tilestats, ntiles, M, C, gamma, stats, dgamma, dbeta,
-                       coef, accumulate);
-    STIL_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(bn_bwd_tiles_stage1_kernel, dim3(cdiv(C, 32), nsplit), dim3(256), 0, s, tilestats, ntiles, C, cdiv(ntiles, nsplit),
-                       (double*)workspace);
-    STIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_tiles_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, nsplit, M, C, gamma, stats,
-                       dgamma, dbeta, coef, accumulate);
-    STIL_LAUNCH_CHECK();
-  }
-  long total4 = (long)M * C / 4;
-  int grid = (int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid), dim3(256), 0, s, dz, z, x, stats, coef, dx, total4, C, relu);
-  STIL_LAUNCH_CHECK();
-  return STIL_OK;
+  const BnTrainBwd fin{gamma, stats, dgamma, dbeta, coef, accumulate};
+  return bn_bwd_tiles("stil_bn_train_bwd_tiles", fin, dz, z, x, stats, tilestats, ntiles, coef, dx, M, C, relu, workspace, workspace_bytes,
+                      (hipStream_t)stream);
 }
 
 extern "C" int stil_maxpool3x3s2_fwd(const float* x, float* y, unsigned char* idx, int N, int H, int W, int C, int OH,

@@ -1,6 +1,6 @@
 /* C ABI of libstil_hip.so: test-time BatchNorm on a running estimate of the target statistics (RoTTA's robust BatchNorm, Yuan et
  * al., CVPR 2023, "Robust test-time adaptation in dynamic scenarios"; DUA, Mirza et al., CVPR 2022, "The norm must go on").
- * Kept beside its kernels (bn_memory.hip) and out of include/, whose headers form closed ledgers; stil_tta_amd/_lib.py binds it
+ * Kept beside its entry points (bn_memory.hip) and out of include/, whose headers form closed ledgers; stil_tta_amd/_lib.py binds it
  * through MEMORY_HEADERS (tests/test_bnmemory_abi_ledger_cpu.py is this header's ledger).
  * Every entry returns 0 on success (STIL_OK) and a negative code otherwise (message: stil_last_error()).
  * All pointers are device pointers; `stream` is a hipStream_t (NULL = default stream).

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -682,6 +682,74 @@ class bn_memory:
         _bn_memory = self.prev
 
 
+class _BnRule(NamedTuple):
+    """What the active scopes make of one conv+BN layer's BatchNorm (_bn_rule)."""
+    family: str            # "train" (stil_bn_train_*), "prior" (stil_bn_prior_*) or "memory" (stil_bn_memory_fwd*, the prior's backward)
+    rho: object = None     # the batch statistics' share; None: training BatchNorm
+    src: tuple = ()        # train: (running_mean, running_var, num_batches_tracked), None each under frozen_bn_stats; else the (mean, var) read
+    out: tuple = (None, None)   # memory: the (mean, var) written, None each without an update
+    alpha: float = 0.0
+    unbiased: bool = False
+    delta: object = None   # [C] (mu - mean_batch) * rstd, which the prior's backward reads
+
+
+def _bn_rule(rmean, rvar, nbt, C, dev) -> _BnRule:
+    """Resolve the BatchNorm rule of a layer from frozen_bn_stats / bn_prior / bn_memory, once."""
+    if _bn_memory is not None:   # the adaptation's own estimate of the target statistics: the running buffers only name the layer
+        if not _bn_frozen or rmean is None or _bn_prior is not None:
+            raise RuntimeError("ops.bn_memory belongs inside ops.frozen_bn_stats, without ops.bn_prior, and needs the layer's running_mean")
+        mem = _bn_memory
+        src_mean, src_var, out_mean, out_var = mem.mem.layer(rmean)
+        return _BnRule("memory", mem.rho, (src_mean, src_var), (out_mean, out_var) if mem.update else (None, None), mem.alpha,
+                       mem.unbiased, torch.empty((C,), dtype=torch.float32, device=dev))
+    if _bn_prior is not None:   # source-statistics prior: the running buffers are read, never written
+        if not _bn_frozen or rmean is None or rvar is None:
+            raise RuntimeError("ops.bn_prior belongs inside ops.frozen_bn_stats and needs the layer's running statistics")
+        return _BnRule("prior", _bn_prior, (rmean, rvar), delta=torch.empty((C,), dtype=torch.float32, device=dev))
+    if _bn_frozen:   # the batch statistics normalise as usual; the running buffers are left as they are
+        return _BnRule("train", src=(None, None, None))
+    return _BnRule("train", src=(rmean, rvar, nbt))
+
+
+def _bn_fwd_call(rule, tiles, y, ts, tile_rows, gamma, beta, resid, rstats, z, stats, M, C, relu):
+    """The BatchNorm forward of a conv+BN layer under `rule`.  tiles: statistics from the per-tile partials `ts` the conv GEMM's
+    epilogue left (stil_bn_*_fwd_tiles) instead of two passes over y (stil_bn_*_fwd)."""
+    L = lib()
+    assert tiles or rstats is None
+    nb = L.bn_tiles_workspace_bytes(M, C, tile_rows) if tiles else L.bn_workspace_bytes(M, C)
+    ws = _ws.get(nb, y.device)
+    head = (_p(y), _p(ts), tile_rows, _p(gamma), _p(beta)) if tiles else (_p(y), _p(gamma), _p(beta))
+    res = (_p(resid), _p(rstats)) if tiles else (_p(resid),)
+    src = tuple(_p(t) for t in rule.src)
+    sfx = "_tiles" if tiles else ""
+    if rule.family == "train":
+        getattr(L, "bn_train_fwd" + sfx)(*head, *src, *res, _p(z), _p(stats), M, C, 1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
+        return
+    if rule.family == "memory":
+        fn, src = getattr(L, "bn_memory_fwd" + sfx), src + (_p(rule.out[0]), _p(rule.out[1]), rule.alpha, int(rule.unbiased))
+    else:
+        fn = getattr(L, "bn_prior_fwd" + sfx)
+    fn(*head, *src, rule.rho, *res, _p(z), _p(stats), _p(rule.delta), M, C, 1 if relu else 0, 1e-5, _p(ws), nb, _stream())
+
+
+def _bn_bwd_call(rho, delta, tiles, gz, z, y, gamma, stats, dy, gres, dgamma, dbeta, coef, M, C, relu_mode, acc):
+    """The BatchNorm backward of a conv+BN layer: the prior's when the forward ran at a share rho (ops.bn_prior, ops.bn_memory), else
+    training's.  tiles: (part, nt), the per-tile sums the consumer's input-gradient GEMM left (stil_bn_*_bwd_tiles), or None for
+    the reduction pass over gz and y (stil_bn_*_bwd), which also writes the residual branch's gradient gres."""
+    L = lib()
+    nb = L.bn_workspace_bytes(M, C)
+    ws = _ws.get(nb, gz.device)
+    fam = "bn_train_bwd" if rho is None else "bn_prior_bwd"
+    head = (_p(gz), _p(z), _p(y), _p(gamma), _p(stats)) + (() if rho is None else (_p(delta), rho))
+    if tiles is not None:
+        part, nt = tiles
+        nb = L.bn_bwd_tiles_workspace_bytes(nt, C)
+        ws = _ws.get(nb + 8, gz.device)
+        getattr(L, fam + "_tiles")(*head, _p(part), nt, _p(dy), _p(dgamma), _p(dbeta), _p(coef), M, C, relu_mode, acc, _p(ws), nb, _stream())
+    else:
+        getattr(L, fam)(*head, _p(dy), _p(gres), _p(dgamma), _p(dbeta), _p(coef), M, C, relu_mode, acc, _p(ws), nb, _stream())
+
+
 class ConvBnActFn(torch.autograd.Function):
     """z = relu?( BN_train(conv(x, w)) + residual? ) on NHWC activations.
 
@@ -749,49 +817,9 @@ class ConvBnActFn(torch.autograd.Function):
         assert fused or not defer, "deferred BatchNorm needs the epilogue statistics (can_defer_bn)"
         # deferred: no z.  Under parity tracing the tests still want this layer's ReLU decisions: z is materialised for them
         z = None if (defer and _trace is None) else torch.empty((M, Cout), dtype=torch.float32, device=dev)
-        rho = delta = mem = None
-        if _bn_memory is not None:   # the adaptation's own estimate of the target statistics: the running buffers only name the layer
-            if not _bn_frozen or rmean is None or _bn_prior is not None:
-                raise RuntimeError("ops.bn_memory belongs inside ops.frozen_bn_stats, without ops.bn_prior, and needs the layer's running_mean")
-            mem = _bn_memory
-            rho, delta = mem.rho, torch.empty((Cout,), dtype=torch.float32, device=dev)
-            src_mean, src_var, out_mean, out_var = mem.mem.layer(rmean)
-            if not mem.update:
-                out_mean = out_var = None
-        elif _bn_prior is not None:   # source-statistics prior: the running buffers are read, never written
-            if not _bn_frozen or rmean is None or rvar is None:
-                raise RuntimeError("ops.bn_prior belongs inside ops.frozen_bn_stats and needs the layer's running statistics")
-            rho, delta = _bn_prior, torch.empty((Cout,), dtype=torch.float32, device=dev)
-            src_mean, src_var = rmean, rvar
-        if _bn_frozen:   # the batch statistics normalise as usual; the running buffers are left as they are
-            rmean = rvar = nbt = None
-        if fused:
-            nb = lib().bn_tiles_workspace_bytes(M, Cout, tile_rows)
-            ws = _ws.get(nb, dev)
-            if mem is not None:
-                lib().bn_memory_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(src_mean), _p(src_var), _p(out_mean), _p(out_var),
-                                          mem.alpha, int(mem.unbiased), rho, _p(resid), _p(rstats), _p(z), _p(stats), _p(delta), M, Cout,
-                                          1 if relu else 0, 1e-5, _p(ws), nb, _stream())
-            elif rho is not None:
-                lib().bn_prior_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(rstats),
-                                         _p(z), _p(stats), _p(delta), M, Cout, 1 if relu else 0, 1e-5, _p(ws), nb, _stream())
-            else:
-                lib().bn_train_fwd_tiles(_p(y), _p(ts), tile_rows, _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(rstats), _p(z),
-                                         _p(stats), M, Cout, 1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
-        else:
-            assert rstats is None
-            nb = lib().bn_workspace_bytes(M, Cout)
-            ws = _ws.get(nb, dev)
-            if mem is not None:
-                lib().bn_memory_fwd(_p(y), _p(gamma), _p(beta), _p(src_mean), _p(src_var), _p(out_mean), _p(out_var), mem.alpha,
-                                    int(mem.unbiased), rho, _p(resid), _p(z), _p(stats), _p(delta), M, Cout, 1 if relu else 0, 1e-5,
-                                    _p(ws), nb, _stream())
-            elif rho is not None:
-                lib().bn_prior_fwd(_p(y), _p(gamma), _p(beta), _p(src_mean), _p(src_var), rho, _p(resid), _p(z), _p(stats), _p(delta), M, Cout,
-                                   1 if relu else 0, 1e-5, _p(ws), nb, _stream())
-            else:
-                lib().bn_train_fwd(_p(y), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(nbt), _p(resid), _p(z), _p(stats), M, Cout,
-                                   1 if relu else 0, 1e-5, 0.1, _p(ws), nb, _stream())
+        rule = _bn_rule(rmean, rvar, nbt, Cout, dev)
+        rho, delta = rule.rho, rule.delta
+        _bn_fwd_call(rule, fused, y, ts, tile_rows, gamma, beta, resid, rstats, z, stats, M, Cout, relu)
         if _trace is not None and relu:
             _trace["relu"][id(gamma)] = z.view(Nb, OH, OW, Cout)
         ctx.save_for_backward(x, w, gamma, beta, y, None if defer else z, stats, xstats, delta)
@@ -833,8 +861,6 @@ class ConvBnActFn(torch.autograd.Function):
         premasked = ctx.premask_out is not None and ctx.premask_out.get("masked", False)   # gz already carries the (z > 0) mask
         gres = torch.empty((M, Cout), dtype=torch.float32, device=dev) if (has_res and relu and not premasked) else None
         coef = torch.empty((3, Cout), dtype=torch.float32, device=dev)
-        nb = lib().bn_workspace_bytes(M, Cout)
-        ws = _ws.get(nb, dev)
         gslot, bslot = getattr(gamma, "_gslot", None), getattr(beta, "_gslot", None)
         dgamma = gslot if gslot is not None else torch.empty_like(gamma)
         dbeta = bslot if bslot is not None else torch.empty_like(beta)
@@ -842,23 +868,11 @@ class ConvBnActFn(torch.autograd.Function):
         relu_mode = 0 if premasked else ((1 if has_res else 2) if relu else 0)
         cell = ctx.bstat_recv
         part = cell.get("part") if cell is not None else None
-        if part is not None and gres is None and tuple(part.shape) == (2 * cell["nt"], Cout) and (cell["mode"] == 2) == (relu_mode == 2) \
-                and (cell["mode"] != 0 or premasked):
-            # the consumer's input-gradient GEMM left the per-tile sums: no reduction pass over gz and y
-            nb2 = lib().bn_bwd_tiles_workspace_bytes(cell["nt"], Cout)
-            ws2 = _ws.get(nb2 + 8, dev)
-            if rho is not None:
-                lib().bn_prior_bwd_tiles(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(delta), rho, _p(part), cell["nt"], _p(dy), _p(dgamma),
-                                         _p(dbeta), _p(coef), M, Cout, relu_mode, acc, _p(ws2), nb2, _stream())
-            else:
-                lib().bn_train_bwd_tiles(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(part), cell["nt"], _p(dy), _p(dgamma), _p(dbeta), _p(coef), M,
-                                         Cout, relu_mode, acc, _p(ws2), nb2, _stream())
-        elif rho is not None:
-            lib().bn_prior_bwd(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(delta), rho, _p(dy), _p(gres), _p(dgamma), _p(dbeta), _p(coef), M,
-                               Cout, relu_mode, acc, _p(ws), nb, _stream())
-        else:
-            lib().bn_train_bwd(_p(gz), _p(z), _p(y), _p(gamma), _p(stats), _p(dy), _p(gres), _p(dgamma), _p(dbeta), _p(coef), M,
-                               Cout, relu_mode, acc, _p(ws), nb, _stream())
+        # tiles: the consumer's input-gradient GEMM left the per-tile sums, so no reduction pass over gz and y
+        tiles = part is not None and gres is None and tuple(part.shape) == (2 * cell["nt"], Cout) and (cell["mode"] == 2) == (relu_mode == 2) \
+            and (cell["mode"] != 0 or premasked)
+        _bn_bwd_call(rho, delta, (part, cell["nt"]) if tiles else None, gz, z, y, gamma, stats, dy, gres, dgamma, dbeta, coef, M, Cout,
+                     relu_mode, acc)
         if gslot is not None:
             _touch(gamma)
             _touch(beta)

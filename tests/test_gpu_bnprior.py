@@ -135,8 +135,9 @@ class _Case:
         dz = self.ops.gemm_nt(self.dz_ops[0], self.dz_ops[1], M, C, 16, relu_mask=zmask, bstats=(self.y, stats, part, mode, 0))
         return dz, part, nt
 
-    def bwd(self, path, rho, stats, delta, dz, z, relu, part=None, nt=0, gout=False, accumulate=0, legacy=False):
-        """-> (dx [M+1, C], gout [M+1, C] or None, dgamma [C + 4], dbeta [C + 4])"""
+    def bwd(self, path, rho, stats, delta, dz, z, relu, part=None, nt=0, gout=False, accumulate=0, legacy=False, ws_offset=0):
+        """-> (dx [M+1, C], gout [M+1, C] or None, dgamma [C + 4], dbeta [C + 4]); ws_offset (two-pass): bytes the workspace pointer is
+        moved past its 16-byte aligned start (4: the scalar final instead of the float4 one)"""
         L, M, C = self.L, self.M, self.C
         dx, go = _buf(M, C), (_buf(M, C) if gout else None)
         dga, dbe = torch.full((C + 4,), SENT, device="cuda"), torch.full((C + 4,), SENT, device="cuda")
@@ -154,13 +155,15 @@ class _Case:
                                      _p(coef), M, C, relu, accumulate, _p(ws), nb, None)
         else:
             nb = L.bn_workspace_bytes(M, C)
-            ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+            ws = torch.empty(nb + 16, dtype=torch.uint8, device="cuda")
+            wp = ws.data_ptr() + ws_offset
+            assert wp % 16 == ws_offset, "the allocator's alignment decides which final runs"
             if legacy:
                 L.bn_train_bwd(_p(dz), _p(z), _p(self.y), _p(self.gamma), _p(stats), _p(dx), _p(go), _p(dga), _p(dbe), _p(coef), M, C, relu,
-                               accumulate, _p(ws), nb, None)
+                               accumulate, wp, nb, None)
             else:
                 L.bn_prior_bwd(_p(dz), _p(z), _p(self.y), _p(self.gamma), _p(stats), _p(delta), rho, _p(dx), _p(go), _p(dga), _p(dbe), _p(coef),
-                               M, C, relu, accumulate, _p(ws), nb, None)
+                               M, C, relu, accumulate, wp, nb, None)
         torch.cuda.synchronize()
         return dx, go, dga, dbe
 
@@ -261,6 +264,30 @@ def test_entry_points_against_float64(cases, M, C, rho):
                     close(dbe[:C], dbr + (c.dinit[1].double() if acc else 0.0), name=tag + " dbeta")
                     if gout:
                         assert bool((go[M] == SENT).all()) and torch.equal(go[:M].double(), g), tag + " gout"
+
+
+@pytest.mark.parametrize("M,C", [(49, 64), (1000, 64)])
+def test_scalar_backward_final_against_float64(cases, M, C):
+    """A two-pass backward whose workspace is not 16-byte aligned finishes its sums with the scalar final (8 lanes) instead of the
+    float4 one (32 lanes): stil_bn_train_bwd and stil_bn_prior_bwd (rho = 0.2), aligned and 4 bytes off, against the float64
+    reference and bar of test_entry_points_against_float64.  The two finals add in different orders: not bit-equal to each other."""
+    c = cases(M, C)
+    gam = c.gamma.double()
+    dz = c.ops.gemm_nt(c.dz_ops[0], c.dz_ops[1], M, C, 16)
+    for legacy, rho in ((True, 1.0), (False, 0.2)):
+        zp, stats, delta = c.fwd("two_pass", rho, None, None, 1, legacy=legacy)
+        zr = c.fwd("two_pass", rho, c.resid, None, 1, legacy=legacy)[0]
+        _, xhat, _, r, dl = c.ref_fwd(rho, None, None, 1, zp[:M] > 0)
+        for relu, zc, mask in ((2, None, zp[:M] > 0), (1, zr, zr[:M] > 0)):
+            dxr, dgr, dbr = closed_form_backward(dz.double() * mask, xhat, gam, r, dl, rho)
+            for acc in (0, 1):
+                for off in (0, 4):
+                    dx, _, dga, dbe = c.bwd("two_pass", rho, stats, delta, dz, zc, relu, accumulate=acc, legacy=legacy, ws_offset=off)
+                    tag = f"{'train' if legacy else 'prior'} relu={relu} acc={acc} workspace+{off}"
+                    assert bool((dx[M] == SENT).all()) and bool((dga[C:] == SENT).all()) and bool((dbe[C:] == SENT).all()), tag
+                    close(dx[:M], dxr, name=tag + " dx")
+                    close(dga[:C], dgr + (c.dinit[0].double() if acc else 0.0), name=tag + " dgamma")
+                    close(dbe[:C], dbr + (c.dinit[1].double() if acc else 0.0), name=tag + " dbeta")
 
 
 @pytest.mark.parametrize("M,C", SHAPES)

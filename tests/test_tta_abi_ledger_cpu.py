@@ -33,7 +33,7 @@ LEDGERS = {
     "stil_bnprior.h": {
         "stil_bn_prior_fwd": [_BN_F64, _BN_RHO1, _BN_BAD],
         "stil_bn_prior_fwd_tiles": [_BN_F64, _BN_RHO1, _BN_BAD],
-        "stil_bn_prior_bwd": [_BN_F64, _BN_RHO1, _BN_BAD],
+        "stil_bn_prior_bwd": [_BN_F64, _BN_RHO1, _BN_BAD, "test_gpu_bnprior.py::test_scalar_backward_final_against_float64"],
         "stil_bn_prior_bwd_tiles": [_BN_F64, _BN_RHO1, _BN_BAD],
     },
     "stil_infomax.h": {
