@@ -37,3 +37,4 @@ extern "C" int stil_device_count(void) {
 #include "deyo.hip"
 #include "sar.hip"
 #include "read.hip"
+#include "cgpl.hip"

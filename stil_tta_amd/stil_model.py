@@ -49,6 +49,7 @@ _DEFAULTS = dict(
                          # | "shot_im" (Liang et al., ICML 2020: entropy plus a batch-diversity term) | "bn_adapt" (forward only: BatchNorm statistics re-estimated on the test batch, nothing updated)
                          # | "marginal_entropy" (MEMO, Zhang et al., NeurIPS 2022: adapts on augmented views of each sample, scores the clean batch after the update)
                          # | "read" (Yang et al., ICLR 2024: the encoders frozen, the fusion attention's Q/K/V projection adapted; needs tta_params "fusion")
+                         # | "cgpl" (STiL's own consensus pseudo-labels over out_m, out_i, out_t on the test batch; below)
                          # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
@@ -90,6 +91,11 @@ _DEFAULTS = dict(
     # tta_div_weight x the batch-balance term of "shot_im" (tta_div_eps inside its logarithm; 0 switches it off).  Form and defaults as recalled: unpinned
     tta_read_gamma=None,           # gamma in (0, 1]: rows above it are pushed, rows below it damped; None = exp(-1), where the row loss is -c ln c.
                                    # READ's published Adam rate is 1e-4 (as recalled: unpinned); tta_lr keeps its own default.  tta_bn_prior / tta_bn_momentum are refused
+    # "cgpl" only: STiL's own unlabelled-data branch (CGPL, PGLS, three soft cross-entropies; STiLModel.py:255-303 with the student's own outputs as the
+    # label source) run on the test batch.  temperature and the prototypes are the checkpoint's; DA is not applied at test time (its queue belongs to training)
+    tta_pl_threshold=None,         # rows whose smoothed confidence reaches it are learned from; None = th1
+    tta_pl_rate=None,              # weight in [0, 1] of the consensus label against the prototype classifier's; None = rate_pseudo; 1: prototypes and projector never run
+    tta_pl_seed=2025,              # seed of the coins that hand a case-3 row to the imaging or the tabular head, drawn on the device per adapted batch
 )
 
 
@@ -678,6 +684,8 @@ class STiLModel(_Base):
         of the batch and the clean batch is then scored in eval mode on that estimate: forward only, nothing else is adapted.
         With "read" (tta.read_step) the encoders run as here, in eval mode under no_grad, and only the last fusion layer's Q/K/V
         projection adapts (tta_params "fusion"); the scores are those of that forward, before the update.
+        With "cgpl" (tta.cgpl_step) the batch runs STiL's own unlabelled-data branch on all three heads' logits: consensus pseudo-labels,
+        prototype smoothing, one soft cross-entropy per head; the scores are those of the adapting forward, before the update.
         With tta_bn_momentum every method but "read" normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)

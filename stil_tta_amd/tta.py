@@ -17,6 +17,8 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
                            Adam over A gated by n > 0 -> recovery of A when the running mean of the loss falls below tta_sar_reset
     read_step              its own pass (`fusion_pass`): the encoders in eval mode under no_grad, then the fusion layers and heads
                            under grad with read_loss -> Adam over A = the last fusion layer's qkv weight and bias (tta_params "fusion")
+    cgpl_step              the pass with all three heads' logits kept: cgpl_loss (STiL's own consensus pseudo-labels over out_m, out_i,
+                           out_t, smoothed by the prototypes) -> Adam over A gated by n > 0
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
     dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
@@ -24,7 +26,7 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
 With tta_bn_momentum every forward above normalises on the BatchNorm memory (`BnMemory`, model._bn_mem: a running estimate of the
 target statistics in RoTTA's manner, Yuan et al., CVPR 2023) in place of the checkpoint's statistics: all forwards of a batch read
 the same estimate, exactly one of them writes the update, and the step commits it at its end.
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState`) lives in
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState` / `CgplState`) lives in
 `model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
 shuffles (`DeyoState.rng`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
@@ -96,6 +98,11 @@ def check_hparams(hp):
     _number(hp, "tta_read_gamma", 0, strict=True, also=(None,))
     if hp.tta_read_gamma is not None and hp.tta_read_gamma > 1:
         raise ValueError(f"tta_read_gamma must not exceed 1, not {hp.tta_read_gamma!r}")
+    _number(hp, "tta_pl_threshold", 0, also=(None,))
+    _number(hp, "tta_pl_rate", 0, also=(None,))
+    if hp.tta_pl_rate is not None and hp.tta_pl_rate > 1:
+        raise ValueError(f"tta_pl_rate must not exceed 1, not {hp.tta_pl_rate!r}")
+    _int_from(hp, "tta_pl_seed", 0)
     if hp.tta_method == "read" and hp.tta_params != "fusion":
         raise ValueError(f"tta_method 'read' adapts the fusion attention alone: set tta_params 'fusion' (this model: {hp.tta_params!r})")
     if hp.tta_params == "fusion" and hp.tta_method != "read":
@@ -134,22 +141,27 @@ def param_names(model) -> List[str]:
 
 # ---------------------------------------------------------------------------------------------- losses
 class _RowLossFn(torch.autograd.Function):
-    """The one autograd node of the seven losses below: launch(z) -> (loss, probabilities or None, dZ) makes the loss's single
+    """The one autograd node of the losses below: launch(z) -> (loss, probabilities or None, dZ) makes the loss's single
     library call, which forms dZ in the same launch sequence; the probabilities carry no gradient and backward scales dZ by the
-    incoming gradient."""
+    incoming gradient.  Given further logit tensors after `launch`, launch takes the tuple of them all and returns one dZ per
+    tensor."""
 
     @staticmethod
-    def forward(ctx, z, launch):
-        loss, p, dz = launch(z)
-        ctx.save_for_backward(dz)
+    def forward(ctx, z, launch, *more):
+        if more:   # several logit tensors (cgpl_loss): launch((z, ...)) -> (loss, p, (dZ, ...)), one gradient per tensor
+            loss, p, dzs = launch((z,) + more)
+            ctx.save_for_backward(*dzs)
+        else:
+            loss, p, dz = launch(z)
+            ctx.save_for_backward(dz)
         if p is not None:
             ctx.mark_non_differentiable(p)
         return loss, p
 
     @staticmethod
     def backward(ctx, g, _gp=None):
-        (dz,) = ctx.saved_tensors
-        return _scale_by(dz, g), None
+        dz, *more = ctx.saved_tensors
+        return (_scale_by(dz, g), None) + tuple(_scale_by(d, g) for d in more)
 
 
 def _empty(z, n, dtype, count=None):
@@ -346,6 +358,68 @@ def read_loss(z, gamma=math.exp(-1.0), div_weight=1.0, eps=1e-5):
         return out[0], p, dz
 
     return _RowLossFn.apply(z.contiguous(), launch) + (info,)
+
+
+def cgpl_rate(hp) -> float:
+    """tta_pl_rate resolved: None -> rate_pseudo, the weight of the consensus label against the prototype classifier's"""
+    return float(hp.rate_pseudo if hp.tta_pl_rate is None else hp.tta_pl_rate)
+
+
+def cgpl_threshold(hp) -> float:
+    """tta_pl_threshold resolved: None -> th1"""
+    return float(hp.th1 if hp.tta_pl_threshold is None else hp.tta_pl_threshold)
+
+
+def cgpl_loss(zm, zi, zt, feat, protos, coin, rate, T, th, active=None, gate=None):
+    """STiL's own loss on unlabelled rows (STiLModel.py:255-303 with use_ema False) beside eata_entropy, on the logits of the
+    three heads: the case of every row from which heads agree on the first maximum (1: all three; 2_i: multimodal and imaging;
+    2_t: multimodal and tabular; 3: otherwise), the pseudo-label q = rate softmax(mean logits of the agreeing heads) + (1 - rate)
+    softmax(feat . protos^T / T), the confidence max_k (rate softmax(zm) + (1 - rate) tp) >= th, and per head the soft
+    cross-entropy -sum_k q_k log softmax(z_h)_k over the rows its case assigns to it (multimodal: case 1; imaging: 1, 2_t, 3 with
+    coin; tabular: 1, 2_i, 3 without), each summed and divided by ALL rows; q carries no gradient.  All in stil_cgpl_rows: n and the
+    gate of the Adam step stay on the device.  feat (the normalised multimodal projection) and protos may be None when rate == 1.
+    -> (the sum of the three losses [autograd w.r.t. zm, zi, zt], softmax(zm) [no grad], info); updates gate;
+    info = dict(loss_m, loss_i, loss_t, pseudo_label, conf, flags [rows, 4: case 1..4, mask1, mask1, 0], ce3, counts [n, case 1,
+    2_i, 2_t, 3], lse3)."""
+    info = {}
+    rate = float(rate)
+    smooth = rate < 1.0
+    if smooth:
+        if feat is None or protos is None:
+            raise ValueError(f"cgpl_loss: rate = {rate} < 1 needs the projection and the prototypes")
+        feat, protos = feat.detach().contiguous(), protos.detach().contiguous()
+
+    def launch(zs):
+        zm, zi, zt = zs
+        _chk(zm, zi, zt, coin, active, gate, *((feat, protos) if smooth else ()))
+        R, K = zm.shape
+        if tuple(zi.shape) != (R, K) or tuple(zt.shape) != (R, K):
+            raise ValueError(f"cgpl_loss: logits of shapes {tuple(zm.shape)}, {tuple(zi.shape)}, {tuple(zt.shape)}")
+        if coin.dtype != torch.uint8 or coin.numel() != R:
+            raise ValueError(f"cgpl_loss: {coin.numel()} {coin.dtype} coins for {R} rows")
+        Dp = 1
+        if smooth:
+            Dp = feat.shape[1]
+            if tuple(feat.shape) != (R, Dp) or tuple(protos.shape) != (K, Dp):
+                raise ValueError(f"cgpl_loss: projection {tuple(feat.shape)} against prototypes {tuple(protos.shape)} for {R} rows of {K} classes")
+        dev = zm.device
+        lse3 = torch.empty((3, R), dtype=torch.float64, device=dev)
+        ce3 = torch.empty((3, R), dtype=torch.float32, device=dev)
+        p, q = torch.empty_like(zm), torch.empty_like(zm)
+        dzs = tuple(torch.empty_like(zm) for _ in range(3))
+        conf = _empty(zm, R, torch.float32)
+        flags = torch.empty((R, 4), dtype=torch.uint8, device=dev)
+        counts = torch.empty((5,), dtype=torch.int32, device=dev)
+        out = _empty(zm, 4, torch.float32)
+        ws = _empty(zm, R * K, torch.float64) if smooth else None
+        nt = 0 if active is None else active.numel()
+        lib().cgpl_rows(_p(zm), _p(zi), _p(zt), K, _p(feat) if smooth else None, _p(protos) if smooth else None, _p(coin), R, K, Dp,
+                        float(T), rate, float(th), 1.0 / R, _p(lse3), _p(p), _p(q), K, _p(conf), _p(flags), _p(ce3), _p(dzs[0]), _p(dzs[1]),
+                        _p(dzs[2]), K, _p(counts), _p(out), _p(active), _p(gate), nt, _p(ws), _stream())
+        info.update(loss_m=out[1], loss_i=out[2], loss_t=out[3], pseudo_label=q, conf=conf, flags=flags, ce3=ce3, counts=counts, lse3=lse3)
+        return out[0], p, dzs
+
+    return _RowLossFn.apply(zm.contiguous(), launch, zi.contiguous(), zt.contiguous()) + (info,)
 
 
 def marginal_entropy(z, groups, views, want_probs=False):
@@ -618,6 +692,17 @@ class DeyoState(TentState):
         return out
 
 
+class CgplState(TentState):
+    """TentState plus what the consensus pseudo-label step adds: the gated copy of the Adam mask (`gate` = active and n > 0,
+    written by stil_cgpl_rows) and the device counter of the coins' generator, one per adapted batch: reset() leaves it running,
+    drop() forgets it."""
+
+    def __init__(self, flat: FlatState, names: List[str]):
+        super().__init__(flat, names)
+        self.gate = torch.zeros_like(self.active)
+        self.coin_step = torch.zeros(1, dtype=torch.int64, device=flat.params.device)
+
+
 def bn_momentum(hp, t: int) -> float:
     """alpha_t of the t-th update of the BatchNorm memory, t = 1, 2, ...: min(1, tta_bn_momentum x tta_bn_momentum_decay^t +
     tta_bn_momentum_min), DUA's schedule (Mirza et al., CVPR 2022); with the default decay 1 and minimum 0 it is tta_bn_momentum."""
@@ -719,6 +804,8 @@ def _state(model) -> TentState:
             model._tent = DeyoState(model.flat, names, model.hp.tta_shuffle_seed)
         elif model.hp.tta_method == "sar":
             model._tent = SarState(model.flat, names)
+        elif model.hp.tta_method == "cgpl":
+            model._tent = CgplState(model.flat, names)
         else:
             model._tent = TentState(model.flat, names)
         if model.hp.tta_method == "marginal_entropy":
@@ -793,11 +880,12 @@ def _bn_scope(model, B, update):
     return ops.bn_memory(mem, mem.alpha if N is None else B / (N + B), mem.alpha, unbiased=False, update=update)
 
 
-def _forward(model, x_img, x_tab, update=False):
-    """The adapting forward -> out_m: no MI-layer dropout; BatchNorm over the B images of this batch by `_bn_scope`'s rule (a short
-    last batch gets its own rho), running buffers untouched."""
+def _forward(model, x_img, x_tab, update=False, outputs="m"):
+    """The adapting forward -> out_m (outputs "all": the 10-tuple of forward_all, out_m first): no MI-layer dropout; BatchNorm over
+    the B images of this batch by `_bn_scope`'s rule (a short last batch gets its own rho), running buffers untouched."""
     with ops.frozen_bn_stats(), _bn_scope(model, x_img.shape[0], update):
-        return model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)[0]
+        outs = model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)
+        return outs if outputs == "all" else outs[0]
 
 
 def _score_forward(model, x_img, x_tab, update=False):
@@ -826,17 +914,19 @@ def _grads_of(model, st):
             q.requires_grad_(f)
 
 
-def adapting_pass(model, x, st, loss_fn, update=True):
+def adapting_pass(model, x, st, loss_fn, update=True, outputs="m"):
     """One adapting forward and backward on the inputs x = (images, table, ...) of a batch: the forward of `_forward`,
-    loss_fn(out_m) -> (loss, probs, extras), gradients of the loss for A only (no weight-gradient products) in st.grads.
+    loss_fn(out_m) -> (loss, probs, extras) (outputs "all": loss_fn takes the whole 10-tuple of forward_all), gradients of the
+    loss for A only (no weight-gradient products) in st.grads.
     Writes st.grads and whatever loss_fn writes and, with tta_bn_momentum and `update`, the back buffer of the BatchNorm memory
     (a constant of the backward); never a parameter, BatchNorm buffer, teacher, prototype or training slab.
     The caller holds torch.inference_mode(False).  -> (out_m, loss, probs, extras), detached."""
     x_img, x_tab = _inputs(model, x)
     with _grads_of(model, st):
-        out_m = _forward(model, x_img, x_tab, update)
-        loss, probs, extras = loss_fn(out_m)
+        outs = _forward(model, x_img, x_tab, update, outputs)
+        loss, probs, extras = loss_fn(outs)
         loss.backward()
+    out_m = outs[0] if outputs == "all" else outs
     return out_m.detach(), loss.detach(), probs, extras
 
 
@@ -1089,6 +1179,49 @@ def read_step(model, batch):
         return model._score_test(probs, y)
 
 
+def cgpl_step(model, batch):
+    """STiL's own semi-supervised branch (CGPL, PGLS and the three soft cross-entropies, STiLModel.py:255-303 with use_ema False:
+    the pseudo-labels come from the student's own detached outputs) run on one test batch, every row taken as unlabelled: (1) TENT's
+    forward, all ten outputs of forward_all kept; (2) under no_grad and unless the rate is 1, the normalised multimodal projection of
+    cat(e_si, e_c, e_st); (3) one coin per row, drawn on the device from (tta_pl_seed, the state's batch counter); (4) cgpl_loss with
+    rate = tta_pl_rate (None: rate_pseudo), th = tta_pl_threshold (None: th1), T = temperature and the checkpoint's prototypes;
+    (5) one backward through all three heads, gradients for A only (no weight-gradient products); (6) one Adam step over A if and only
+    if n > 0 rows reach the threshold: n, the counts and that gate stay on the device, the step reads nothing back.  The modality
+    heads act here: a row whose tabular head disagrees with the other two (case 2_i) pulls that head alone towards their consensus,
+    and with tta_params "norm" that gradient reaches the tabular encoder's LayerNorms through out_t; under an image shift the roles
+    swap.  Not part of this method: the checkpoint's EMA teacher as the label source, any update of the prototypes, the ITC, CLUB and
+    prototype losses, and distribution alignment (hp.DA is not applied at test time: its queue belongs to training).  Writes what
+    tent_step writes; tta_bn_prior and tta_bn_momentum compose as for tent_step.  The scores are softmax(out_m) of this forward,
+    before the update.  The coin counter runs on through reset_tta() and episodes and is dropped with the state by load_state_dict.
+    last_tta: loss, loss_m, loss_i, loss_t, y_hat_m, y_hat_i, y_hat_t, probs, pseudo_label, conf, flags, coin, counts, all on the
+    device."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        rate, th = cgpl_rate(hp), cgpl_threshold(hp)
+        heads = {}
+
+        def loss_fn(outs):
+            zm, zi, zt, e_si, _, _, e_st, _, _, e_c = outs
+            feat = None
+            if rate < 1.0:
+                with torch.no_grad():
+                    feat = model.project_3features(torch.cat((e_si.detach(), e_c.detach(), e_st.detach()), dim=1))[0]
+            coin = ops.rng_mask((zm.shape[0],), 0.5, hp.tta_pl_seed, 0, zm.device, st.coin_step)
+            heads.update(y_hat_i=zi.detach(), y_hat_t=zt.detach(), coin=coin)
+            return cgpl_loss(zm, zi, zt, feat, model.prototypes, coin, rate, float(hp.temperature), th, st.active, st.gate)
+
+        out_m, loss, probs, info = adapting_pass(model, x, st, loss_fn, outputs="all")
+        lib().counter_inc(_p(st.coin_step), _stream())
+        st.adam_step(hp.tta_lr, mask=st.gate)
+        _commit_memory(model)
+        model.last_tta = dict(loss=loss, loss_m=info["loss_m"], loss_i=info["loss_i"], loss_t=info["loss_t"], y_hat_m=out_m,
+                              y_hat_i=heads["y_hat_i"], y_hat_t=heads["y_hat_t"], probs=probs, pseudo_label=info["pseudo_label"],
+                              conf=info["conf"], flags=info["flags"], coin=heads["coin"], counts=info["counts"])
+        return model._score_test(probs, y)
+
+
 def bn_adapt_step(model, batch):
     """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
     statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
@@ -1141,7 +1274,7 @@ def dua_step(model, batch):
 
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
          "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step,
-         "read": read_step}   # tta_method -> STiLModel.test_step's body
+         "read": read_step, "cgpl": cgpl_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
