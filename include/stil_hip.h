@@ -104,6 +104,9 @@ int stil_gemm_nt_variant(int M, int N, int tune);
  * and the kernel's geometry code is compiled out) + 1000000 * a_bn (the operand-staging BatchNorm instantiation) + 10000000 * b3 (the
  * split-precision instantiation, tune + 100000) */
 int stil_gemm_nt_config(const float* A, const float* W, int M, int N, int K, int lda, int ldb, int srcC, int KH, int KW, int plain, int a_bn, int tune);
+/* the column-panel width (in 64-column tiles) of the tile order an unsplit 64x64-tile launch of [M,N,K] takes, 0 = row-tile major
+ * (the rule under "Tile order" above; host only, no GPU call) */
+int stil_gemm_nt_panel(int M, int N, int K);
 
 /* Weight gradient  dW (+)= dY[M,N]^T . Xgather[M,K]  (split over M, slab partials + ordered reduce).
  * KH*KW > 1: dW is written in the reference layout (N, srcC, KH, KW); else [N, Kdst] (first Kdst columns).
@@ -114,6 +117,14 @@ int stil_wgrad_tn(const float* dY, const float* X, float* dW, int M, int N, int 
                   int Kdst, int accumulate, const float* x_bn, float* workspace, size_t workspace_bytes, int tune, void* stream);
 /* `x_bn` (optional): as stil_gemm_nt's a_bn, for the X operand (the raw conv output of the producing layer and its
  * statistics block [4][srcC]). */
+/* the instantiation stil_wgrad_tn / stil_wgrad_tn_partial launch for these operands (host only, no GPU call; the launcher decides
+ * by the same function), as a CONFIG code, or < 0 where the entry point refuses them (a bad tune, x_bn without 16-byte operands):
+ *   tile (11 = gemm_tn_kernel<1,1> 64x64, 12 = <1,2> 64x128: the 128-wide variant at N <= 64, 22 = <2,2> 128x128)
+ *   + 100 * vec (16-byte loads: dY, X 16-byte aligned, ldy, ldx, srcC, N, K % 4 == 0) + 1000 * x_bn (the operand-staging BatchNorm
+ *   instantiation; x_bn != 0 says the operand is given) + 10000 * reduce4 (1: wgrad_reduce4_kernel finishes the product -- K % 4
+ *   == 0, whole 4-channel quads per tap, a 16-byte aligned workspace --, 0: wgrad_reduce_kernel; _partial launches neither). */
+int stil_wgrad_config(const float* dY, const float* X, int M, int N, int K, int ldy, int ldx, int srcC, int KH, int KW,
+                      int x_bn, const void* workspace, int tune);
 /* DEFERRED reductions (small per-GPU batches under hipGraph replay: the step is ~1000 dependent launches of ~5 us): the _partial
  * entry points leave only the slab partials ([stil_wgrad_splits][N][K] / [stil_colsum_chunks][N]) in a workspace the CALLER keeps
  * until it has passed one StilReduceJob per product to stil_reduce_jobs, which finishes all of them in ceil(n / 48) launches -- bit

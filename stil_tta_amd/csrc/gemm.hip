@@ -531,8 +531,11 @@ void gemm_nt_kernel(GemmNTArgs p) {
   constexpr int FLUSH = 64 / BK;   // k-tiles per partial chain (ACC2)
 
   // Interior fast path (block-uniform): single-tap gathers (plain GEMM, 1x1 conv) whose tile lies fully inside M x N
-  // and whose K is a multiple of BK need no predicate at all -> unconditional 16-byte loads, pointer += BK.
-  const bool full = VEC && ntaps == 1 && (PLAIN || g.mode == 0) && (g.C % BK == 0) && (tm + 1) * BM <= p.M && (tn + 1) * BN <= p.N;
+  // and whose K is a multiple of BK need no predicate at all -> unconditional 16-byte loads, pointer += BK.  A single tap can still
+  // fall outside the source (a padded 1x1 gather, or an output grid larger than the strided source): those rows are zero, which
+  // only the guarded path knows.
+  const bool tap_inside = PLAIN || (g.pad_y == 0 && g.pad_x == 0 && (g.OH - 1) * g.stride < g.H && (g.OW - 1) * g.stride < g.W);
+  const bool full = VEC && ntaps == 1 && (PLAIN || g.mode == 0) && tap_inside && (g.C % BK == 0) && (tm + 1) * BM <= p.M && (tn + 1) * BN <= p.N;
   auto mainloop = [&](auto full_tag) {
     constexpr bool FULL = decltype(full_tag)::value;
     auto load = [&]() {
@@ -1468,6 +1471,7 @@ static int nt_panel(int M, int N, int K) {
   (void)M;
   return gw > 1 ? gw : 0;
 }
+extern "C" int stil_gemm_nt_panel(int M, int N, int K) { return nt_panel(M, N, K); }
 
 // bytes of the split-K workspace stil_gemm_nt wants for this product (0: the product is not split).  Layout: a FIXED ticket
 // region of NT_SPLIT_TICKET_BYTES (one int per tile; split products have at most NT_SPLIT_MAX_TILES tiles) then [tiles][splits][64*64] float
@@ -1548,6 +1552,11 @@ extern "C" int stil_gemm_nt(const float* A, const float* W, float* C, int M, int
   const bool single = (cfg / 100) % 10 == 2; // ... with one LDS buffer (64x64 tiles only)
   const bool acc2 = (cfg / 1000) % 10 == 1;  // long reductions: two-level accumulation (see gemm_nt_kernel)
   const bool vec = (cfg / 10000) % 10 == 1;
+  // BatchNorm + ReLU of the producing layer applied while A is staged: 64x64 tiles (or the lean 128x128 kernel), vector loads, BK = 16
+  // or the lean kernel's 32 -- refused here, before the first HIP call
+  STIL_REQUIRE(!a_bn || (vec && !bk32 && mode == 0 && srcC % 16 == 0 && srcC <= 2048 && (tune % 100 == 0 || tune % 100 == 11 || tune % 100 == 44)),
+               "stil_gemm_nt: a_bn runs 64x64 tiles only (tune %% 100 must be 0 or 11: the caller sizes colstats by "
+               "stil_gemm_nt_tile_rows) and needs 16-byte aligned operands, a forward gather, Cin %% 16 == 0 and Cin <= 2048 (Cin=%d)", srcC);
   rc = gemm_nt_attr();
   if (rc) return rc;
   if (variant == 11 && p.splits == 1) p.panel = nt_panel(M, N, K);
@@ -1569,10 +1578,7 @@ extern "C" int stil_gemm_nt(const float* A, const float* W, float* C, int M, int
     STIL_LAUNCH_CHECK();
     return STIL_OK;
   }
-  if (a_bn) {   // BatchNorm + ReLU of the producing layer applied while A is staged: 64x64 tiles, vector loads, BK = 16 only
-    STIL_REQUIRE(vec && !bk32 && mode == 0 && srcC % 16 == 0 && srcC <= 2048 && (tune % 100 == 0 || tune % 100 == 11 || tune % 100 == 44),
-                 "stil_gemm_nt: a_bn runs 64x64 tiles only (tune %% 100 must be 0 or 11: the caller sizes colstats by "
-                 "stil_gemm_nt_tile_rows) and needs 16-byte aligned operands, a forward gather, Cin %% 16 == 0 and Cin <= 2048 (Cin=%d)", srcC);
+  if (a_bn) {   // 64x64 tiles, vector loads, BK = 16 only (argument check above)
     const dim3 grid_(cdiv(M, 64) * cdiv(N, 64) * p.splits);
     if (want_b3 && srcC % 32 == 0 && K % 32 == 0 && !scalar_epilogue) {   // split-precision mode: 32-deep k-tiles, two-level sums
       const size_t lds3_ = (size_t)3 * 128 * 40 * 2 + (size_t)3 * srcC * sizeof(float);
@@ -1658,6 +1664,23 @@ extern "C" size_t stil_wgrad_workspace_bytes(int M, int N, int K, int tune) {
   return (size_t)wgrad_splits(M, N, K, tune) * N * K * sizeof(float);
 }
 
+// The instantiation stil_wgrad_tn launches for these operands (include/stil_hip.h: stil_wgrad_config), < 0 where it refuses them:
+// tile (11 = 64x64, 12 = 64x128 for N <= 64 under the 128-wide variant, 22 = 128x128) + 100 * vec (16-byte loads) + 1000 * x_bn
+// + 10000 * reduce4 (wgrad_reduce4_kernel finishes the product; 0 = wgrad_reduce_kernel).  wgrad_tn_impl launches by this code.
+static int wgrad_config(const float* dY, const float* X, int M, int N, int K, int ldy, int ldx, int srcC, int KH, int KW,
+                        int x_bn, const void* workspace, int tune) {
+  if (!(tune == 0 || tune == 11 || tune == 22)) return -1;
+  const bool vec = is_vec(dY, ldy) && is_vec(X, ldx) && (srcC % 4 == 0) && (N % 4 == 0) && (K % 4 == 0);
+  if (x_bn && !vec) return -1;
+  const int tile = tn_variant(M, N, K, tune) == 11 ? 11 : (N <= 64 ? 12 : 22);
+  const bool reduce4 = K % 4 == 0 && (KH * KW == 1 || srcC % 4 == 0) && ((uintptr_t)workspace % 16) == 0;
+  return tile + 100 * (vec ? 1 : 0) + 1000 * (x_bn ? 1 : 0) + 10000 * (reduce4 ? 1 : 0);
+}
+extern "C" int stil_wgrad_config(const float* dY, const float* X, int M, int N, int K, int ldy, int ldx, int srcC, int KH, int KW,
+                                 int x_bn, const void* workspace, int tune) {
+  return wgrad_config(dY, X, M, N, K, ldy, ldx, srcC, KH, KW, x_bn, workspace, tune);
+}
+
 // dW (+)= dY^T . Xgather ; dW laid out [N, Kdst] (taps==1) or (N, Cin, KH, KW) (taps>1)
 extern "C" int stil_wgrad_splits(int M, int N, int K, int tune) { return wgrad_splits(M, N, K, tune); }
 static int wgrad_tn_impl(const float* dY, const float* X, float* dW, int M, int N, int K, int ldy, int ldx,
@@ -1680,14 +1703,16 @@ static int wgrad_tn_impl(const float* dY, const float* X, float* dW, int M, int 
   p.vecX = is_vec(X, ldx) && (srcC % 4 == 0);
   p.xbn = x_bn;
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = p.vecY && p.vecX && (N % 4 == 0) && (K % 4 == 0);
-  STIL_REQUIRE(!x_bn || (vec && srcC % 4 == 0), "stil_wgrad_tn: x_bn needs 16-byte aligned operands and Cin %% 4 == 0");
-  if (tn_variant(M, N, K, tune) == 11) {
+  const int cfg = wgrad_config(dY, X, M, N, K, ldy, ldx, srcC, KH, KW, x_bn ? 1 : 0, workspace, tune);
+  STIL_REQUIRE(cfg >= 0, "stil_wgrad_tn: x_bn needs 16-byte aligned operands and Cin %% 4 == 0");
+  const int tile = cfg % 100;
+  const bool vec = (cfg / 100) % 10 == 1;
+  if (tile == 11) {
     dim3 grid(cdiv(N, 64) * cdiv(K, 64) * splits);
     if (x_bn) hipLaunchKernelGGL((gemm_tn_kernel<1, 1, true, true>), grid, dim3(256), 0, s, p);
     else if (vec) hipLaunchKernelGGL((gemm_tn_kernel<1, 1, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((gemm_tn_kernel<1, 1, false>), grid, dim3(256), 0, s, p);
-  } else if (N <= 64) {
+  } else if (tile == 12) {
     dim3 grid(cdiv(N, 64) * cdiv(K, 128) * splits);
     if (x_bn) hipLaunchKernelGGL((gemm_tn_kernel<1, 2, true, true>), grid, dim3(256), 0, s, p);
     else if (vec) hipLaunchKernelGGL((gemm_tn_kernel<1, 2, true>), grid, dim3(256), 0, s, p);
@@ -1702,7 +1727,7 @@ static int wgrad_tn_impl(const float* dY, const float* X, float* dW, int M, int 
   if (!dW) return STIL_OK;     // stil_wgrad_tn_partial: the caller reduces the slabs later (stil_reduce_jobs)
   long total = (long)N * K;
   int taps = KH * KW;
-  if (K % 4 == 0 && (taps == 1 || srcC % 4 == 0) && ((uintptr_t)workspace % 16) == 0)
+  if (cfg / 10000 == 1)
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(cdiv(total / 4, 32)), dim3(256), 0, s, workspace, dW, splits, N, K, srcC,
                        taps, Kdst, accumulate);
   else

@@ -28,27 +28,35 @@ _MET = "test_gpu_metrics.py"
 _ATT = "test_gpu_attention.py"
 _ATT_CPU = "test_attention_config_cpu.py"
 KE = "test_gpu_kernel_edges.py"
+_GEMM = "test_gpu_gemm.py"
+_GEMM_CPU = "test_gemm_cases_cpu.py"
+_GEMM_NT = f"{_GEMM}::test_gemm_nt_instantiations_against_float64"
+_GEMM_WG = f"{_GEMM}::test_wgrad_instantiations_against_float64"
+_GEMM_CODES = f"{_GEMM_CPU}::test_every_case_reports_the_code_its_table_names"
+_GEMM_SPLITS = f"{_GEMM_CPU}::test_splits_slabs_and_panels_are_what_the_cases_claim"
 
 # name -> list of "file::function" (checked directly there) | str (the reason it has no test of its own)
 LEDGER = {
     "stil_last_error": [_INFO],
     "stil_version": [_INFO, f"{CPU}::test_library_exports_every_declared_symbol"],
     "stil_device_count": [_INFO],
-    "stil_gemm_nt": [f"{OPS}::test_gemm_nt_plain", f"{OPS}::test_conv_fwd_dgrad_wgrad", f"{OPS}::test_gemm_nt_wide_epilogue_is_the_scalar_one_bit_for_bit"],
-    "stil_gemm_nt_split_workspace_bytes": [f"{OPS}::test_gemm_split_k_is_the_unsplit_product_and_deterministic"],
-    "stil_gemm_nt_force_splits": [_POLICY],
+    "stil_gemm_nt": [_GEMM_NT, f"{_GEMM}::test_documented_exact_relations_hold_bit_for_bit", f"{_GEMM_CPU}::test_argument_checks_refuse_before_any_launch",
+                     f"{OPS}::test_gemm_nt_plain", f"{OPS}::test_conv_fwd_dgrad_wgrad", f"{OPS}::test_gemm_nt_wide_epilogue_is_the_scalar_one_bit_for_bit"],
+    "stil_gemm_nt_split_workspace_bytes": [_GEMM_SPLITS, _GEMM_NT, f"{OPS}::test_gemm_split_k_is_the_unsplit_product_and_deterministic"],
+    "stil_gemm_nt_force_splits": [_GEMM_SPLITS, _GEMM_NT, _POLICY],
     "stil_gemm_nt_bstats_ok": "eligibility predicate of the bstats epilogue (no arithmetic); the launches it admits are compared in "
                               "test_gemm_epilogue_batchnorm_backward_sums",
     "stil_gemm_nt_tile_rows": [_BN_STATS, f"{CPU}::test_gemm_tune_policy_and_precision_flag_arithmetic"],
     "stil_gemm_nt_variant": [f"{CPU}::test_c_abi_rejects_bad_arguments_without_a_gpu", f"{CPU}::test_gemm_tune_policy_and_precision_flag_arithmetic"],
-    "stil_gemm_nt_config": "reports which instantiation a launch takes (bench bookkeeping and profile labels, no arithmetic); read on every "
-                           "ops.gemm_nt call of the GEMM tests",
+    "stil_gemm_nt_config": [_GEMM_CODES, _GEMM_NT],
+    "stil_gemm_nt_panel": [_GEMM_SPLITS],
     "stil_wgrad_workspace_bytes": [_INFO],
-    "stil_wgrad_tn": [f"{OPS}::test_conv_fwd_dgrad_wgrad", _DEFER],
+    "stil_wgrad_tn": [_GEMM_WG, f"{_GEMM_CPU}::test_argument_checks_refuse_before_any_launch", f"{OPS}::test_conv_fwd_dgrad_wgrad", _DEFER],
+    "stil_wgrad_config": [_GEMM_CODES, _GEMM_WG],
     "stil_reduce_job_bytes": [_POLICY],
     "stil_wgrad_splits": [_POLICY, _INFO],
-    "stil_wgrad_force_splits": [_POLICY],
-    "stil_wgrad_tn_partial": [_DEFER],
+    "stil_wgrad_force_splits": [_GEMM_SPLITS, _GEMM_WG, _POLICY],
+    "stil_wgrad_tn_partial": [_GEMM_WG, _DEFER],
     "stil_colsum_chunks": [_INFO, _POLICY],
     "stil_colsum_partial": [_DEFER],
     "stil_reduce_jobs": [_DEFER, "test_gpu_graph_step.py::test_deferred_reduce_duplicate_slot_at_low_offset"],
