@@ -255,7 +255,8 @@ int stil_tokmean_fwd(const float* x, float* y, int B, int T, int D, void* stream
 int stil_tokmean_bwd(const float* g, float* dx, int B, int T, int D, void* stream);
 
 /* ---- SAINT tabular encoder (config_dvm_STiL_SAINT): STiLModel_SAINT_backbone.py:159-184, SAINT/model_util.py:43-59,79-122
- * token j < ncat+1 of out [B,nfeats,d]: embeds[(j ? int(x[b,cat_cols[j-1]]) : 0) + cat_offsets[j]] + pos_enc[j];
+ * token j < ncat+1 of out [B,nfeats,d]: embeds[(j ? int(x[b,cat_cols[j-1]]) : 0) + cat_offsets[j]] + pos_enc[j]
+ * (pos_enc and d_pos need ncat+1 rows: rows 0..ncat are read / written; cat_cols may be NULL only with ncat == 0);
  * tokens tok0+j: the per-continuous-column simple_MLP(1 -> hid -> d), all columns in ONE launch (the reference loops in
  * Python); param_ptrs / grad_ptrs are device arrays of ncon*4 pointers {w1[hid], b1[hid], W2[d,hid], b2[d]}. */
 int stil_saint_embed_fwd(const float* x, const int* cat_cols, const int* cat_offsets, const float* embeds,

@@ -180,7 +180,8 @@ extern "C" int stil_saint_embed_fwd(const float* x, const int* cat_cols, const i
 extern "C" int stil_saint_embed_bwd(const float* g, const float* x, const int* cat_cols, const int* cat_offsets,
                                     const int* rowcol, int n_emb_rows, float* d_embeds, float* d_pos, int B, int ncols,
                                     int ncat, int nfeats, int d, int accumulate, void* stream) {
-  STIL_REQUIRE(g && x && cat_offsets && rowcol && d_embeds && d_pos, "stil_saint_embed_bwd: null pointer");
+  STIL_REQUIRE(g && x && cat_offsets && rowcol && d_embeds && d_pos && (ncat == 0 || cat_cols),
+               "stil_saint_embed_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(saint_embed_bwd_emb_kernel, dim3(n_emb_rows), dim3(64), 0, s, g, x, cat_cols, cat_offsets, rowcol,
                      d_embeds, B, ncols, nfeats, d, accumulate);

@@ -1006,6 +1006,9 @@ extern "C" int stil_tab_embed_bwd(const float* g, const float* x, const int* cat
                                   float* d_colemb, int B, int ncols, int ncat, int D, int accumulate, float* workspace,
                                   size_t workspace_bytes, void* stream) {
   STIL_REQUIRE(g && x && d_cls && d_colemb && workspace, "stil_tab_embed_bwd: null pointer");
+  STIL_REQUIRE(ncols == ncat || (d_con_w && d_con_b), "stil_tab_embed_bwd: null continuous pointers");
+  const bool cat = ncat > 0 && n_emb_rows > 0;
+  STIL_REQUIRE(!cat || (cat_offsets && rowcol && d_emb), "stil_tab_embed_bwd: null categorical pointers");
   STIL_REQUIRE(workspace_bytes >= stil_tab_embed_bwd_workspace_bytes(ncols, D), "stil_tab_embed_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(tab_embed_bwd_tok_kernel, dim3(ncols + 1), dim3(256), 0, s, g, x, d_colemb, workspace, B, ncols,
@@ -1014,8 +1017,7 @@ extern "C" int stil_tab_embed_bwd(const float* g, const float* x, const int* cat
   hipLaunchKernelGGL(tab_embed_bwd_fin_kernel, dim3(cdiv(D, 64)), dim3(64), 0, s, workspace, d_cls, d_con_w, d_con_b,
                      ncols, ncat, D, accumulate);
   STIL_LAUNCH_CHECK();
-  if (ncat > 0 && n_emb_rows > 0) {
-    STIL_REQUIRE(cat_offsets && rowcol && d_emb, "stil_tab_embed_bwd: null categorical pointers");
+  if (cat) {
     hipLaunchKernelGGL(tab_embed_bwd_emb_kernel, dim3(n_emb_rows), dim3(256), 0, s, g, x, cat_offsets, rowcol, d_emb, B,
                        ncols, D, accumulate);
     STIL_LAUNCH_CHECK();

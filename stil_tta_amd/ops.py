@@ -1520,6 +1520,11 @@ class SaintEmbedColMlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, embeds, pos, meta, *mlp_params):
+        # the kernels read pos rows 0..ncat and the backward writes d_pos rows 0..ncat: with no continuous column the
+        # reference's table has ncat rows only (its own positional lookup raises there too)
+        if pos.shape[0] < meta["ncat"] + 1:
+            raise RuntimeError(f"SaintEmbedColMlpFn: pos has {pos.shape[0]} rows, the CLS and categorical tokens need "
+                               f"ncat + 1 = {meta['ncat'] + 1}")
         _chk(x, embeds, pos)
         B, ncols = x.shape
         d = embeds.shape[1]

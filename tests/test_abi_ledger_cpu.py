@@ -34,6 +34,9 @@ _GEMM_NT = f"{_GEMM}::test_gemm_nt_instantiations_against_float64"
 _GEMM_WG = f"{_GEMM}::test_wgrad_instantiations_against_float64"
 _GEMM_CODES = f"{_GEMM_CPU}::test_every_case_reports_the_code_its_table_names"
 _GEMM_SPLITS = f"{_GEMM_CPU}::test_splits_slabs_and_panels_are_what_the_cases_claim"
+_TAB = "test_gpu_tabular.py"
+_TAB_REFUSE = "test_tabular_cases_cpu.py::test_argument_checks_refuse_before_any_launch"
+_TAB_OWN = f"{_TAB}::test_each_forward_stays_inside_its_own_tokens"
 
 # name -> list of "file::function" (checked directly there) | str (the reason it has no test of its own)
 LEDGER = {
@@ -95,15 +98,17 @@ LEDGER = {
     "stil_axpby": [f"{EP}::test_axpby_and_scale_dev"],
     "stil_rng_mask": [f"{OPS}::test_rng_mask_rate_and_determinism", f"{KE}::test_rng_mask_equals_the_integer_model_byte_for_byte", f"{KE}::test_rng_mask_offset_continues_the_stream"],
     "stil_counter_inc": [f"{OPS}::test_rng_mask_rate_and_determinism", f"{KE}::test_rng_mask_equals_the_integer_model_byte_for_byte"],
-    "stil_tab_embed_fwd": [f"{OPS}::test_tab_embed"],
-    "stil_tab_embed_bwd_workspace_bytes": [_INFO],
-    "stil_tab_embed_bwd": [f"{OPS}::test_tab_embed"],
+    "stil_tab_embed_fwd": [f"{_TAB}::test_tab_embed_against_float64", _TAB_REFUSE, f"{OPS}::test_tab_embed"],
+    "stil_tab_embed_bwd_workspace_bytes": [_INFO, f"{_TAB}::test_tab_embed_against_float64", _TAB_REFUSE],
+    "stil_tab_embed_bwd": [f"{_TAB}::test_tab_embed_against_float64", _TAB_REFUSE, f"{OPS}::test_tab_embed"],
     "stil_tokmean_fwd": [f"{EP}::test_tokmean"],
     "stil_tokmean_bwd": [f"{EP}::test_tokmean"],
-    "stil_saint_embed_fwd": [f"{OPS}::test_saint_pieces"],
-    "stil_saint_embed_bwd": [f"{OPS}::test_saint_pieces"],
-    "stil_colmlp_fwd": [f"{OPS}::test_saint_pieces"],
-    "stil_colmlp_bwd": [f"{OPS}::test_saint_pieces"],
+    "stil_saint_embed_fwd": [f"{_TAB}::test_saint_embed_against_float64", _TAB_OWN, _TAB_REFUSE, f"{OPS}::test_saint_pieces"],
+    "stil_saint_embed_bwd": [f"{_TAB}::test_saint_embed_against_float64", _TAB_REFUSE, f"{OPS}::test_saint_pieces"],
+    "stil_colmlp_fwd": [f"{_TAB}::test_colmlp_against_float64", f"{_TAB}::test_colmlp_follows_its_pointer_tables", _TAB_OWN, _TAB_REFUSE,
+                        f"{OPS}::test_saint_pieces"],
+    "stil_colmlp_bwd": [f"{_TAB}::test_colmlp_against_float64", f"{_TAB}::test_colmlp_follows_its_pointer_tables", _TAB_REFUSE,
+                        f"{OPS}::test_saint_pieces"],
     "stil_geglu_fwd": [f"{EP}::test_geglu"],
     "stil_geglu_bwd": [f"{EP}::test_geglu"],
     "stil_row_softmax_fwd": [f"{EP}::test_row_softmax"],
