@@ -569,12 +569,22 @@ class IndexLoader:
     builder's rows in chunks of `batch_size` (the last partial chunk is kept, like DataLoader's drop_last=False)."""
 
     def __init__(self, builder, batch_size: int, shuffle: bool = True, seed: int = 2022, drop_last: bool = False, rank: int = 0,
-                 world: int = 1):
+                 world: int = 1, order: Optional[torch.Tensor] = None):
         """rank / world: the DistributedSampler Lightning installs under DDP -- every rank draws the SAME permutation (common
-        seed), pads it to a multiple of `world` by wrapping around and takes every world-th row starting at its rank."""
+        seed), pads it to a multiple of `world` by wrapping around and takes every world-th row starting at its rank.
+        order: a fixed row order (one index per row of the builder, e.g. shift.class_ordered) used in every epoch instead of
+        arange / randperm; `shuffle` is then ignored and the generator is not drawn from."""
         self.builder, self.bs, self.shuffle, self.drop_last = builder, int(batch_size), bool(shuffle), bool(drop_last)
         self.rank, self.world = int(rank), int(world)
         self.gen = torch.Generator().manual_seed(seed)
+        self.order = None
+        if order is not None:
+            order = torch.as_tensor(order).detach().cpu()
+            n = len(builder)
+            if order.dtype not in (torch.int64, torch.int32) or order.dim() != 1 or order.numel() != n or \
+                    (n and not (0 <= int(order.min()) and int(order.max()) < n)):
+                raise ValueError(f"order must hold one row index in [0, {n}) per row of the builder: an integer tensor [{n}]")
+            self.order = order.to(torch.int64).clone()
 
     def _rows(self):
         n = len(self.builder)
@@ -586,7 +596,10 @@ class IndexLoader:
 
     def __iter__(self):
         n = len(self.builder)
-        order = torch.randperm(n, generator=self.gen) if self.shuffle else torch.arange(n)
+        if self.order is not None:
+            order = self.order
+        else:
+            order = torch.randperm(n, generator=self.gen) if self.shuffle else torch.arange(n)
         if self.world > 1:
             total = self._rows() * self.world
             order = torch.cat([order, order[: total - n]])[self.rank::self.world]

@@ -38,3 +38,4 @@ extern "C" int stil_device_count(void) {
 #include "sar.hip"
 #include "read.hip"
 #include "cgpl.hip"
+#include "shift.hip"

@@ -271,11 +271,9 @@ def fit(model, train_loaders: Dict[str, Iterable], val_loader: Optional[Iterable
                 launch=step.launch if step is not None else None)
 
 
-def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Optional[int] = None, tta_fisher_loader=None,
-         tta_fisher_batches: Optional[int] = None) -> Dict[str, float]:
-    """Trainer.test(model, loader, ckpt_path=best) of trainers/evaluate.py:206-213 / trainers/test.py:85-90.
-    tta_fisher_loader (tta_method "eata"): batches of source-like data in the test loader's layout; after the checkpoint load and
-    before the first test batch, model.estimate_tta_fisher takes EATA's Fisher estimate from (the first tta_fisher_batches of) it."""
+def _prepare_test(model, ckpt_path, tta_fisher_loader, tta_fisher_batches):
+    """What a test run does once, before its first batch: the checkpoint load, freeze() and (tta_method "eata") the Fisher estimate
+    from tta_fisher_loader.  -> the model's device."""
     model.setup_device()
     if ckpt_path is not None:
         load_checkpoint(ckpt_path, model)
@@ -286,10 +284,55 @@ def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Opt
         if n is None and hasattr(tta_fisher_loader, "__len__"):
             n = len(tta_fisher_loader)
         model.estimate_tta_fisher((_to_device(b, dev) for b in tta_fisher_loader), n)
+    return dev
+
+
+def _run_test(model, test_loader, dev, limit_batches: Optional[int], shift=None) -> Dict[str, float]:
+    """One pass of the test metrics over the loader: metrics reset, every batch through test_step (after one ShiftStream of
+    `shift`, when there is one), -> test_epoch_end()'s metrics."""
+    stream = None
+    if shift is not None:
+        from .shift import ShiftStream
+        stream = ShiftStream(shift)
     model.acc_test.reset()
     model.auc_test.reset()
     for i, batch in enumerate(test_loader):
         if limit_batches is not None and i >= limit_batches:
             break
-        model.test_step(_to_device(batch, dev), i)
+        batch = _to_device(batch, dev)
+        model.test_step(batch if stream is None else stream(batch), i)
     return {k: float(v) for k, v in model.test_epoch_end().items()}
+
+
+def test(model, test_loader, ckpt_path: Optional[str] = None, limit_batches: Optional[int] = None, tta_fisher_loader=None,
+         tta_fisher_batches: Optional[int] = None, shift=None) -> Dict[str, float]:
+    """Trainer.test(model, loader, ckpt_path=best) of trainers/evaluate.py:206-213 / trainers/test.py:85-90.
+    tta_fisher_loader (tta_method "eata"): batches of source-like data in the test loader's layout; after the checkpoint load and
+    before the first test batch, model.estimate_tta_fisher takes EATA's Fisher estimate from (the first tta_fisher_batches of) it.
+    shift (a shift.ShiftSpec): every batch goes through one shift.ShiftStream of it on the device before test_step sees it;
+    None (default) runs the loader's batches as they are."""
+    dev = _prepare_test(model, ckpt_path, tta_fisher_loader, tta_fisher_batches)
+    return _run_test(model, test_loader, dev, limit_batches, shift)
+
+
+def test_shifts(model, test_loader, shifts, ckpt_path: Optional[str] = None, protocol: str = "reset", limit_batches: Optional[int] = None,
+                tta_fisher_loader=None, tta_fisher_batches: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+    """The table of a test-time adaptation paper: the loader under every shift of `shifts` ({name: shift.ShiftSpec}, in order)
+    -> {name: metrics, ..., "mean": the mean of each metric over the shifts}.  The checkpoint load, freeze() and the Fisher
+    estimate happen once; per shift the metrics are reset and the loader runs through one fresh ShiftStream.
+    protocol "reset": model.reset_tta() before every shift, so each starts from the source model (the per-corruption protocol);
+    "continual": never, the adapted model carries over from shift to shift (the protocol of CoTTA)."""
+    from .shift import ShiftSpec
+    if protocol not in ("reset", "continual"):
+        raise ValueError(f"protocol {protocol!r} is neither 'reset' nor 'continual'")
+    if not shifts or "mean" in shifts or not all(isinstance(s, ShiftSpec) for s in shifts.values()):
+        raise ValueError("shifts must be a non-empty {name: ShiftSpec} without the name 'mean'")
+    dev = _prepare_test(model, ckpt_path, tta_fisher_loader, tta_fisher_batches)
+    out: Dict[str, Dict[str, float]] = {}
+    for name, spec in shifts.items():
+        if protocol == "reset" and hasattr(model, "reset_tta"):   # a module without test-time adaptation carries nothing over
+            model.reset_tta()
+        out[name] = _run_test(model, test_loader, dev, limit_batches, spec)
+    keys = list(next(iter(out.values())))
+    out["mean"] = {k: sum(m[k] for m in out.values()) / len(out) for k in keys}
+    return out
