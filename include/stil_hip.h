@@ -322,7 +322,9 @@ int stil_proto_commit(float* prototypes, float* prototypes_sum, float* prototype
 /* CoMatch's pseudo-label-graph contrastive loss (models/MatchModel/CoMatch.py:104-117) on S = f_s0 . [f_s1 ; queue_s]^T / T
  * [rows, N] and the pseudo-label graph Q [rows, N] (comatch_model.py:287-297): row_loss[r] = -sum_j log(p_rj + 1e-7) w_rj over
  * the edges Q >= threshold, p = exp(S) / rowsum(exp(S)), w = Q / rowsum(Q over the edges); dS (optional) = d(mean row_loss)/dS
- * with inv_rows = 1/rows. */
+ * with inv_rows = 1/rows.  lds, ldq >= N; ldd >= N is required only with dS.  A row without an edge (possible only with
+ * threshold > 1 or a Q whose diagonal is not 1) returns row_loss = 0 and dS = 0, where the reference's 0/0 gives NaN
+ * (pinned by tests/test_gpu_match_kernels.py::test_contrast_graph_row_without_an_edge_gives_zero). */
 int stil_contrast_graph(const float* S, int lds, const float* Q, int ldq, float threshold, float* row_loss, float* dS,
                         int ldd, int rows, int N, float inv_rows, void* stream);
 /* SimMatch's label unfolding / aggregation (models/MatchModel/simmatch_model.py:289-302): teacher[r,j] = tpo[r,j] * probs[r,

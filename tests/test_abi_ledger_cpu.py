@@ -24,6 +24,8 @@ _INFO = f"{EP}::test_size_queries_and_library_info"
 _AUG = "test_gpu_augment.py"
 _ALB = "test_gpu_augment_alb.py"
 _MATCH = "test_gpu_match.py"
+_MK = "test_gpu_match_kernels.py"
+_MK_CPU = "test_match_cases_cpu.py"
 _MET = "test_gpu_metrics.py"
 _ATT = "test_gpu_attention.py"
 _ATT_CPU = "test_attention_config_cpu.py"
@@ -129,10 +131,17 @@ LEDGER = {
     "stil_proto_accum": [f"{OPS}::test_cgpl_pgls_and_prototypes", f"{KE}::test_proto_accum"],
     "stil_proto_add": [f"{EP}::test_proto_add_and_commit"],
     "stil_proto_commit": [f"{EP}::test_proto_add_and_commit"],
-    "stil_contrast_graph": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch"],
-    "stil_simmatch_unfold": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch"],
-    "stil_freematch_update": [f"{_MATCH}::test_freematch_kernels_against_torch"],
-    "stil_freematch_entropy": [f"{_MATCH}::test_freematch_kernels_against_torch"],
+    "stil_contrast_graph": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch", f"{_MK}::test_contrast_graph_against_float64",
+                            f"{_MK}::test_contrast_graph_row_without_an_edge_gives_zero", f"{_MK}::test_contrast_graph_fn_scales_by_the_upstream_gradient",
+                            f"{_MK_CPU}::test_fp32_aten_meets_the_contrast_checks", f"{_MK_CPU}::test_contrast_graph_refuses_before_any_launch"],
+    "stil_simmatch_unfold": [f"{_MATCH}::test_contrast_graph_and_unfold_kernels_against_torch", f"{_MK}::test_simmatch_unfold_against_float64",
+                             f"{_MK_CPU}::test_fp32_aten_meets_the_unfold_checks", f"{_MK_CPU}::test_simmatch_unfold_refuses_before_any_launch"],
+    "stil_freematch_update": [f"{_MATCH}::test_freematch_kernels_against_torch", f"{_MK}::test_freematch_update_two_calls_against_float64",
+                              f"{_MK_CPU}::test_fp32_aten_meets_the_update_checks_and_rows_are_unambiguous",
+                              f"{_MK_CPU}::test_freematch_update_refuses_before_any_launch"],
+    "stil_freematch_entropy": [f"{_MATCH}::test_freematch_kernels_against_torch", f"{_MK}::test_freematch_entropy_against_float64",
+                               f"{_MK}::test_freematch_entropy_fn_scales_by_the_upstream_gradient", f"{_MK_CPU}::test_fp32_aten_meets_the_entropy_checks",
+                               f"{_MK_CPU}::test_freematch_entropy_refuses_before_any_launch"],
     "stil_flag_ratios": [f"{EP}::test_flag_ratios"],
     "stil_onehot_argmax": [f"{OPS}::test_onehot_argmax_first_maximum_and_threshold", f"{KE}::test_onehot_argmax_beyond_one_wave", f"{KE}::test_onehot_argmax_ties_across_and_within_lanes_and_at_the_threshold"],
     "stil_ema_update": [f"{OPS}::test_ema_and_adam_slabs", f"{KE}::test_ema_update_is_bit_exact_past_the_grid_cap", f"{KE}::test_ema_update_on_a_sub_slab"],
