@@ -38,4 +38,5 @@ extern "C" int stil_device_count(void) {
 #include "sar.hip"
 #include "read.hip"
 #include "cgpl.hip"
+#include "roid.hip"
 #include "shift.hip"

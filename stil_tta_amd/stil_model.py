@@ -50,6 +50,7 @@ _DEFAULTS = dict(
                          # | "marginal_entropy" (MEMO, Zhang et al., NeurIPS 2022: adapts on augmented views of each sample, scores the clean batch after the update)
                          # | "read" (Yang et al., ICLR 2024: the encoders frozen, the fusion attention's Q/K/V projection adapted; needs tta_params "fusion")
                          # | "cgpl" (STiL's own consensus pseudo-labels over out_m, out_i, out_t on the test batch; below)
+                         # | "roid" (Marsden et al., WACV 2024: soft likelihood ratio, weight ensembling with the source, prior correction; below)
                          # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
@@ -96,6 +97,13 @@ _DEFAULTS = dict(
     tta_pl_threshold=None,         # rows whose smoothed confidence reaches it are learned from; None = th1
     tta_pl_rate=None,              # weight in [0, 1] of the consensus label against the prototype classifier's; None = rate_pseudo; 1: prototypes and projector never run
     tta_pl_seed=2025,              # seed of the coins that hand a case-3 row to the imaging or the tabular head, drawn on the device per adapted batch
+    # "roid" only: ROID (Marsden, Doebler, Yang, WACV 2024), the soft likelihood ratio of the rows a diversity selection keeps, weight ensembling with
+    # the source values and a prior correction of the scores.  tta_probs_momentum is the momentum of its running mean prediction.  As recalled: unpinned
+    tta_roid_temperature=1.0 / 3.0,   # tau > 0: a kept row weighs exp(dn cn / tau), dn and cn its min-max normalised diversity and certainty
+    tta_roid_src_momentum=0.99,       # in [0, 1]: after every step A <- this x A + (1 - this) x source values; 1: no pull; 0: A returns to the source
+    tta_roid_clip=0.99,               # in (0, 1): the probabilities are clipped to it inside the likelihood ratio
+    tta_roid_eps=1e-5,                # eps > 0 inside that ratio's logarithm
+    tta_roid_prior_correction=True,   # the reported scores are reweighted by the smoothed batch-mean prediction and renormalised (forward only)
 )
 
 
@@ -686,6 +694,9 @@ class STiLModel(_Base):
         projection adapts (tta_params "fusion"); the scores are those of that forward, before the update.
         With "cgpl" (tta.cgpl_step) the batch runs STiL's own unlabelled-data branch on all three heads' logits: consensus pseudo-labels,
         prototype smoothing, one soft cross-entropy per head; the scores are those of the adapting forward, before the update.
+        With "roid" (tta.roid_step) the batch adapts the model on the soft likelihood ratio of the rows a diversity selection keeps, A
+        is then pulled tta_roid_src_momentum of the way back to its source values, and the scores are those of the adapting forward
+        corrected by the batch's prior (tta_roid_prior_correction), before the update.
         With tta_bn_momentum every method but "read" normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)

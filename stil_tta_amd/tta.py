@@ -19,6 +19,9 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
                            under grad with read_loss -> Adam over A = the last fusion layer's qkv weight and bias (tta_params "fusion")
     cgpl_step              the pass with all three heads' logits kept: cgpl_loss (STiL's own consensus pseudo-labels over out_m, out_i,
                            out_t, smoothed by the prototypes) -> Adam over A gated by n > 0
+    roid_step              roid_loss (ROID, Marsden et al., WACV 2024: the soft likelihood ratio of the rows a diversity selection keeps,
+                           weighted by certainty and diversity) -> Adam over A -> A pulled a fixed fraction of the way back to its
+                           source values (weight ensembling); the reported scores are corrected by the batch's prior, forward only
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
     dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
@@ -26,7 +29,7 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
 With tta_bn_momentum every forward above normalises on the BatchNorm memory (`BnMemory`, model._bn_mem: a running estimate of the
 target statistics in RoTTA's manner, Yuan et al., CVPR 2023) in place of the checkpoint's statistics: all forwards of a batch read
 the same estimate, exactly one of them writes the update, and the step commits it at its end.
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState` / `CgplState`) lives in
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState` / `CgplState` / `RoidState`) lives in
 `model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
 shuffles (`DeyoState.rng`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
@@ -103,6 +106,20 @@ def check_hparams(hp):
     if hp.tta_pl_rate is not None and hp.tta_pl_rate > 1:
         raise ValueError(f"tta_pl_rate must not exceed 1, not {hp.tta_pl_rate!r}")
     _int_from(hp, "tta_pl_seed", 0)
+    _number(hp, "tta_roid_temperature", 0, strict=True)
+    _number(hp, "tta_roid_src_momentum", 0)
+    _number(hp, "tta_roid_clip", 0, strict=True)
+    _number(hp, "tta_roid_eps", 0, strict=True)
+    if hp.tta_roid_src_momentum > 1:
+        raise ValueError(f"tta_roid_src_momentum must not exceed 1, not {hp.tta_roid_src_momentum!r}")
+    if hp.tta_roid_clip >= 1:
+        raise ValueError(f"tta_roid_clip must lie below 1, not {hp.tta_roid_clip!r}")
+    if not isinstance(hp.tta_roid_prior_correction, bool):
+        raise ValueError(f"tta_roid_prior_correction must be True or False, not {hp.tta_roid_prior_correction!r}")
+    if hp.tta_method == "roid":   # the momentum of EATA's running mean, reused for ROID's: checked where ROID reads it
+        _number(hp, "tta_probs_momentum", 0)
+        if hp.tta_probs_momentum > 1:
+            raise ValueError(f"tta_probs_momentum must not exceed 1, not {hp.tta_probs_momentum!r}")
     if hp.tta_method == "read" and hp.tta_params != "fusion":
         raise ValueError(f"tta_method 'read' adapts the fusion attention alone: set tta_params 'fusion' (this model: {hp.tta_params!r})")
     if hp.tta_params == "fusion" and hp.tta_method != "read":
@@ -422,6 +439,42 @@ def cgpl_loss(zm, zi, zt, feat, protos, coin, rate, T, th, active=None, gate=Non
     return _RowLossFn.apply(zm.contiguous(), launch, zi.contiguous(), zt.contiguous()) + (info,)
 
 
+def roid_loss(z, ema, tau=1.0 / 3.0, clip=0.99, eps=1e-5, momentum=0.9, correct=True):
+    """ROID's loss (Marsden, Doebler, Yang, WACV 2024; definition as recalled: unpinned) beside eata_entropy: (1/rows) sum over the
+    kept rows of w_r slr_r, slr_r = -sum_k q_k log(q_k / (1 - q_k) + eps) the soft likelihood ratio of q = min(softmax(z_r), clip).
+    With d_r = 1 - cos(softmax(z_r), ema) (diversity against the running mean prediction `ema` [K], read as it stands before the
+    call) and c_r = -H_r (certainty), both min-max normalised over the batch to dn, cn (a range <= 1e-9 gives 0 for every row: this
+    project's rule), a row is kept unless dn_r lies below the batch mean of dn, and w_r = exp(dn_r cn_r / tau); keep and w carry no
+    gradient.  Then ema <- momentum ema + (1 - momentum) pbar, pbar the batch-mean prediction over all rows, and with `correct` the
+    scores are softmax(z) reweighted by the prior s (from pbar, smoothed) and renormalised.  All in stil_roid_rows: nothing is read back.
+    -> (the weighted soft likelihood ratio [autograd], the corrected scores or with correct False softmax(z) [no grad], info);
+    updates ema; info = dict(H, cos, dn, cn, w, keep, slr, counts [kept, rows, d range degenerate, c range degenerate], pbar, prior,
+    probs, lse)."""
+    info = {}
+
+    def launch(z):
+        _chk(z, ema)
+        R, K = z.shape
+        if ema.dtype != torch.float32 or ema.numel() != K or not ema.is_contiguous():
+            raise ValueError(f"roid_loss: a running mean of {ema.numel()} {ema.dtype} entries for {K} classes")
+        lse = _empty(z, R, torch.float64)
+        h, c, slr, dn, cn, w = _empty(z, R, torch.float32, 6)
+        keep = _empty(z, R, torch.uint8)
+        pbar, prior = _empty(z, K, torch.float32, 2)
+        p, dz = torch.empty_like(z), torch.empty_like(z)
+        scores = torch.empty_like(z) if correct else None
+        counts = torch.empty((4,), dtype=torch.int32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        ws = _empty(z, 4 * R + 2 * K, torch.float64)
+        lib().roid_rows(_p(z), K, R, K, _p(ema), float(tau), float(clip), float(eps), float(momentum), 1.0, int(bool(correct)), _p(lse),
+                        _p(p), K, _p(h), _p(c), _p(slr), _p(dn), _p(cn), _p(w), _p(keep), _p(pbar), _p(prior), _p(scores), K, _p(dz), K,
+                        _p(counts), _p(loss), _p(ws), _stream())
+        info.update(H=h, cos=c, dn=dn, cn=cn, w=w, keep=keep, slr=slr, counts=counts, pbar=pbar, prior=prior, probs=p, lse=lse)
+        return loss, (scores if correct else p), dz
+
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
+
+
 def marginal_entropy(z, groups, views, want_probs=False):
     """MEMO's loss (Zhang, Levine, Finn, NeurIPS 2022) beside entropy: z holds `views` consecutive rows per sample (row g V + v is
     view v of sample g); the loss is the mean over the samples of the entropy of the sample's mean prediction over its views.
@@ -703,6 +756,26 @@ class CgplState(TentState):
         self.coin_step = torch.zeros(1, dtype=torch.int64, device=flat.params.device)
 
 
+class RoidState(CompactState):
+    """CompactState plus what ROID adds (Marsden, Doebler, Yang, WACV 2024): `ema` [K], the running mean prediction the diversity of
+    a row is measured against (1 / K until a batch has moved it), and the weight ensembling of A with its compact source values."""
+
+    def __init__(self, flat: FlatState, names: List[str], num_classes: int):
+        super().__init__(flat, names)
+        self.ema = torch.full((num_classes,), 1.0 / num_classes, dtype=torch.float32, device=flat.params.device)
+
+    @torch.no_grad()
+    def reset(self):
+        """TentState.reset, and the running mean prediction returns to 1 / K."""
+        super().reset()
+        self.ema.fill_(1.0 / self.ema.numel())
+
+    @torch.no_grad()
+    def ensemble(self, momentum: float):
+        """A <- momentum A + (1 - momentum) source values, over A's chunks (stil_roid_ensemble); momentum 1 writes nothing"""
+        lib().roid_ensemble(_p(self.flat.params), _p(self.theta0), *self._slab_args(), float(momentum), _stream())
+
+
 def bn_momentum(hp, t: int) -> float:
     """alpha_t of the t-th update of the BatchNorm memory, t = 1, 2, ...: min(1, tta_bn_momentum x tta_bn_momentum_decay^t +
     tta_bn_momentum_min), DUA's schedule (Mirza et al., CVPR 2022); with the default decay 1 and minimum 0 it is tta_bn_momentum."""
@@ -806,6 +879,8 @@ def _state(model) -> TentState:
             model._tent = SarState(model.flat, names)
         elif model.hp.tta_method == "cgpl":
             model._tent = CgplState(model.flat, names)
+        elif model.hp.tta_method == "roid":
+            model._tent = RoidState(model.flat, names, model.hp.num_classes)
         else:
             model._tent = TentState(model.flat, names)
         if model.hp.tta_method == "marginal_entropy":
@@ -1222,6 +1297,34 @@ def cgpl_step(model, batch):
         return model._score_test(probs, y)
 
 
+def roid_step(model, batch):
+    """ROID (Marsden, Doebler, Yang, WACV 2024, "Universal Test-time Adaptation through Weight Ensembling, Diversity Weighting, and
+    Prior Correction"; definition as recalled: unpinned) on one test batch: (1) TENT's forward and input-gradient-only backward with
+    roid_loss, the soft likelihood ratio of the rows whose diversity against the running mean prediction is not below the batch's
+    mean, weighted by exp(dn cn / tta_roid_temperature) and divided by ALL rows (clip tta_roid_clip, eps tta_roid_eps); the running
+    mean moves at tta_probs_momentum; (2) one Adam step over A; (3) weight ensembling: A <- tta_roid_src_momentum A +
+    (1 - tta_roid_src_momentum) source values after EVERY step, the continuous pull back to the source that needs neither source
+    data nor a trigger (1: off; 0: A returns to the source after every batch); (4) with tta_roid_prior_correction the reported scores
+    are softmax(out_m) reweighted by the smoothed batch-mean prediction and renormalised (forward only: it moves the scores under
+    label shift, never A).  Not part of this method: ROID's consistency branch (a second pass on an augmented view under a
+    symmetric cross-entropy).  Writes what tent_step writes and the running mean; tta_bn_prior, tta_bn_momentum and tta_episodic
+    compose as for tent_step.  The scores come from this forward, before the update.  The step reads nothing back.
+    last_tta: loss, y_hat_m, probs (the reported scores), probs_raw (softmax(out_m)), n_kept, kept, weight, marginal (pbar), prior
+    (s), all on the device."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        out_m, loss, scores, info = adapting_pass(model, x, st, lambda z: roid_loss(
+            z, st.ema, hp.tta_roid_temperature, hp.tta_roid_clip, hp.tta_roid_eps, hp.tta_probs_momentum, hp.tta_roid_prior_correction))
+        st.adam_step(hp.tta_lr)
+        st.ensemble(hp.tta_roid_src_momentum)
+        _commit_memory(model)
+        model.last_tta = dict(loss=loss, y_hat_m=out_m, probs=scores, probs_raw=info["probs"], n_kept=info["counts"][0], kept=info["keep"],
+                              weight=info["w"], marginal=info["pbar"], prior=info["prior"])
+        return model._score_test(scores, y)
+
+
 def bn_adapt_step(model, batch):
     """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
     statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
@@ -1274,7 +1377,7 @@ def dua_step(model, batch):
 
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
          "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step,
-         "read": read_step, "cgpl": cgpl_step}   # tta_method -> STiLModel.test_step's body
+         "read": read_step, "cgpl": cgpl_step, "roid": roid_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
