@@ -39,4 +39,5 @@ extern "C" int stil_device_count(void) {
 #include "read.hip"
 #include "cgpl.hip"
 #include "roid.hip"
+#include "rotta.hip"
 #include "shift.hip"

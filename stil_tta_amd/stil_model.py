@@ -51,6 +51,7 @@ _DEFAULTS = dict(
                          # | "read" (Yang et al., ICLR 2024: the encoders frozen, the fusion attention's Q/K/V projection adapted; needs tta_params "fusion")
                          # | "cgpl" (STiL's own consensus pseudo-labels over out_m, out_i, out_t on the test batch; below)
                          # | "roid" (Marsden et al., WACV 2024: soft likelihood ratio, weight ensembling with the source, prior correction; below)
+                         # | "rotta" (Yuan et al., CVPR 2023: a device-side bank of test samples and an EMA teacher, for class-ordered streams; needs tta_bn_momentum; below)
                          # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
@@ -104,6 +105,13 @@ _DEFAULTS = dict(
     tta_roid_clip=0.99,               # in (0, 1): the probabilities are clipped to it inside the likelihood ratio
     tta_roid_eps=1e-5,                # eps > 0 inside that ratio's logarithm
     tta_roid_prior_correction=True,   # the reported scores are reweighted by the smoothed batch-mean prediction and renormalised (forward only)
+    # "rotta" only: RoTTA (Yuan, Xie, Li, CVPR 2023), for a temporally correlated stream: an EMA teacher scores the batch, a category-balanced bank of
+    # test samples is kept on the device, and the model adapts on the augmented bank (tta_view_policy, tta_view_seed).  Needs tta_bn_momentum (RoTTA:
+    # 0.05), its robust BatchNorm.  As recalled: unpinned
+    tta_rotta_capacity=64,            # N >= 1: the bank's slots (at most 4096)
+    tta_rotta_nu=0.001,               # in [0, 1]: the teacher moves this share of the way to the student after every step
+    tta_rotta_lambda_t=1.0,           # >= 0: weight of a slot's age in its eviction score
+    tta_rotta_lambda_u=1.0,           # >= 0: weight of a slot's uncertainty (the entropy of the teacher's prediction over ln K) in it
 )
 
 
@@ -697,6 +705,8 @@ class STiLModel(_Base):
         With "roid" (tta.roid_step) the batch adapts the model on the soft likelihood ratio of the rows a diversity selection keeps, A
         is then pulled tta_roid_src_momentum of the way back to its source values, and the scores are those of the adapting forward
         corrected by the batch's prior (tta_roid_prior_correction), before the update.
+        With "rotta" (tta.rotta_step) an EMA teacher of A scores the batch (the reported scores) and decides which samples enter a
+        category-balanced bank kept on the device across batches; the model then adapts on the augmented bank against the teacher.
         With tta_bn_momentum every method but "read" normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)

@@ -22,6 +22,10 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
     roid_step              roid_loss (ROID, Marsden et al., WACV 2024: the soft likelihood ratio of the rows a diversity selection keeps,
                            weighted by certainty and diversity) -> Adam over A -> A pulled a fixed fraction of the way back to its
                            source values (weight ensembling); the reported scores are corrected by the batch's prior, forward only
+    rotta_step             RoTTA (Yuan et al., CVPR 2023; as recalled: unpinned): the EMA teacher scores the batch and decides, by
+                           pseudo-label, age and uncertainty, which samples enter a category-balanced bank held on the device
+                           (`RottaState`); the pass then runs on the augmented BANK, not the batch, with rotta_loss against the
+                           teacher's logits of the bank -> Adam over A gated by n > 0 -> the teacher moves tta_rotta_nu towards A
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
     dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
@@ -29,8 +33,8 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
 With tta_bn_momentum every forward above normalises on the BatchNorm memory (`BnMemory`, model._bn_mem: a running estimate of the
 target statistics in RoTTA's manner, Yuan et al., CVPR 2023) in place of the checkpoint's statistics: all forwards of a batch read
 the same estimate, exactly one of them writes the update, and the step commits it at its end.
-A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState` / `CgplState` / `RoidState`) lives in
-`model._tent`, and with it the augmenter of marginal_entropy_step's views (`TentState.views`) and the generator of deyo_step's
+A = the adapted set (`param_names`); the state of an adapting model (`TentState` / `EataState` / `DeyoState` / `SarState` / `CgplState` / `RoidState` / `RottaState`) lives in
+`model._tent`, and with it the augmenter of marginal_entropy_step's and rotta_step's views (`TentState.views`) and the generator of deyo_step's
 shuffles (`DeyoState.rng`).
 Adaptation is rank-local (no collectives) and composes no launch of the training step."""
 from __future__ import annotations
@@ -50,6 +54,7 @@ from .ops import _chk, _p, _scale_by, _stream, join_side
 
 PARAMS = ("bn", "norm", "fusion")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
+ROTTA_MAX_SLOTS = 4096   # STIL_ROTTA_MAX_SLOTS of csrc/stil_rotta.h: the one workgroup that walks the samples bounds the bank
 
 
 def _number(hp, key, lo=None, strict=False, also=()):
@@ -120,6 +125,14 @@ def check_hparams(hp):
         _number(hp, "tta_probs_momentum", 0)
         if hp.tta_probs_momentum > 1:
             raise ValueError(f"tta_probs_momentum must not exceed 1, not {hp.tta_probs_momentum!r}")
+    _int_from(hp, "tta_rotta_capacity", 1)
+    _number(hp, "tta_rotta_nu", 0)
+    _number(hp, "tta_rotta_lambda_t", 0)
+    _number(hp, "tta_rotta_lambda_u", 0)
+    if hp.tta_rotta_nu > 1:
+        raise ValueError(f"tta_rotta_nu must not exceed 1, not {hp.tta_rotta_nu!r}")
+    if hp.tta_rotta_capacity > ROTTA_MAX_SLOTS:
+        raise ValueError(f"tta_rotta_capacity must not exceed {ROTTA_MAX_SLOTS}, the bound of stil_rotta_bank_update, not {hp.tta_rotta_capacity!r}")
     if hp.tta_method == "read" and hp.tta_params != "fusion":
         raise ValueError(f"tta_method 'read' adapts the fusion attention alone: set tta_params 'fusion' (this model: {hp.tta_params!r})")
     if hp.tta_params == "fusion" and hp.tta_method != "read":
@@ -130,6 +143,8 @@ def check_hparams(hp):
                 raise ValueError(f"tta_method 'read' keeps the encoders' normalisation at the source: {key} must be None, not {getattr(hp, key)!r}")
     if hp.tta_method == "dua" and hp.tta_bn_momentum is None:
         raise ValueError("tta_method 'dua' adapts the running estimate of the BatchNorm statistics alone: set tta_bn_momentum (DUA: 0.1)")
+    if hp.tta_method == "rotta" and hp.tta_bn_momentum is None:
+        raise ValueError("tta_method 'rotta' normalises on the running estimate of the BatchNorm statistics, its robust BatchNorm: set tta_bn_momentum (RoTTA: 0.05)")
     if hp.tta_method is not None and hp.tabular_encoder == "saint":
         raise NotImplementedError("test-time adaptation is not implemented for the SAINT tabular encoder")
 
@@ -475,6 +490,39 @@ def roid_loss(z, ema, tau=1.0 / 3.0, clip=0.99, eps=1e-5, momentum=0.9, correct=
     return _RowLossFn.apply(z.contiguous(), launch) + (info,)
 
 
+def rotta_loss(z, zt, label, age, active=None, gate=None):
+    """RoTTA's loss on the bank (Yuan, Xie, Li, CVPR 2023; definition as recalled: unpinned) beside eata_entropy: z the student's
+    logits of the N slots (on their augmented images), zt the teacher's (no gradient), label [N] int32 (-1: an empty slot) and age [N]
+    int32 the bank's bookkeeping.  With n the number of filled slots, loss = (1/n) sum over them of w_i CE(softmax(zt_i), softmax(z_i)),
+    w_i = e_i / (1 + e_i), e_i = exp(-age_i / N) the timeliness weight; dZ = w_i (softmax(z_i) - softmax(zt_i)) / n, exactly 0 on an
+    empty slot; with n == 0 loss and dZ are 0 and the gate closes.  All in stil_rotta_rows: n and the gate of the Adam step stay on
+    the device.
+    -> (the weighted cross-entropy [autograd], None, info); updates gate; info = dict(ce, w, counts [n, N, 0, 0])."""
+    info = {}
+    zt = zt.detach().contiguous()
+
+    def launch(z):
+        _chk(z, zt, label, age, active, gate)
+        R, K = z.shape
+        if tuple(zt.shape) != (R, K):
+            raise ValueError(f"rotta_loss: student logits {tuple(z.shape)} against teacher logits {tuple(zt.shape)}")
+        for name, t in (("label", label), ("age", age)):
+            if t.dtype != torch.int32 or t.numel() != R or not t.is_contiguous():
+                raise ValueError(f"rotta_loss: {name} of {t.numel()} {t.dtype} entries for {R} slots")
+        ce, w = _empty(z, R, torch.float32, 2)
+        dz = torch.empty_like(z)
+        counts = torch.empty((4,), dtype=torch.int32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        ws = _empty(z, 4 * R, torch.float64)
+        nt = 0 if active is None else active.numel()
+        lib().rotta_rows(_p(z), K, _p(zt), K, _p(label), _p(age), R, K, 1.0, _p(ce), _p(w), _p(dz), K, _p(counts), _p(loss), _p(active),
+                         _p(gate), nt, _p(ws), _stream())
+        info.update(ce=ce, w=w, counts=counts)
+        return loss, None, dz
+
+    return _RowLossFn.apply(z.contiguous(), launch) + (info,)
+
+
 def marginal_entropy(z, groups, views, want_probs=False):
     """MEMO's loss (Zhang, Levine, Finn, NeurIPS 2022) beside entropy: z holds `views` consecutive rows per sample (row g V + v is
     view v of sample g); the loss is the mean over the samples of the entropy of the sample's mean prediction over its views.
@@ -776,6 +824,99 @@ class RoidState(CompactState):
         lib().roid_ensemble(_p(self.flat.params), _p(self.theta0), *self._slab_args(), float(momentum), _stream())
 
 
+class RottaState(CompactState):
+    """CompactState plus what RoTTA adds (Yuan, Xie, Li, CVPR 2023): `teacher`, the EMA teacher's values of A, compact like the
+    source values (it equals them at creation and after reset()); the gated copy of the Adam mask (`gate` = active and n > 0,
+    written by stil_rotta_rows); and the bank of N = `capacity` test samples, allocated at the first batch from that batch's shapes,
+    all on the device: bank_img [N, 3, H, W] and bank_tab [N, C] (float32, zero-filled), label [N] (int32, -1: empty), unc [N]
+    (float32), age [N] (int32), occ [K] (int32: filled slots per class), n [1] (int32: the filled slots are the prefix [0, n)) and
+    owner [N] (int32: which sample of the latest batch a slot took, -1: none).  The first sample bank of this module: nothing in it
+    is RoTTA's but the decision rule of stil_rotta_bank_update."""
+
+    def __init__(self, flat: FlatState, names: List[str], num_classes: int, capacity: int):
+        super().__init__(flat, names)
+        self.K, self.capacity = int(num_classes), int(capacity)
+        self.teacher = torch.zeros_like(self.theta0)
+        self.gate = torch.zeros_like(self.active)
+        self.bank_img: Optional[torch.Tensor] = None
+        self.bank_tab: Optional[torch.Tensor] = None
+
+    @torch.no_grad()
+    def snapshot(self):
+        super().snapshot()
+        self.teacher.copy_(self.theta0)
+
+    @torch.no_grad()
+    def reset(self):
+        """TentState.reset; the teacher returns to the source values and the bank is emptied: labels -1, occ, n and age 0, images
+        and table zeroed."""
+        super().reset()
+        if self.source is not None:
+            self.teacher.copy_(self.theta0)
+        if self.bank_img is not None:
+            self.label.fill_(-1)
+            self.owner.fill_(-1)
+            for t in (self.unc, self.age, self.occ, self.n, self.bank_img, self.bank_tab):
+                t.zero_()
+
+    @torch.no_grad()
+    def ensure_bank(self, x_img, x_tab):
+        """the bank, allocated from the first batch's shapes; a batch of other shapes is an error"""
+        N, dev = self.capacity, x_img.device
+        if self.bank_img is None:
+            self.bank_img = torch.zeros((N,) + tuple(x_img.shape[1:]), dtype=torch.float32, device=dev)
+            self.bank_tab = torch.zeros((N,) + tuple(x_tab.shape[1:]), dtype=torch.float32, device=dev)
+            self.label = torch.full((N,), -1, dtype=torch.int32, device=dev)
+            self.owner = torch.full((N,), -1, dtype=torch.int32, device=dev)
+            self.unc = torch.zeros((N,), dtype=torch.float32, device=dev)
+            self.age = torch.zeros((N,), dtype=torch.int32, device=dev)
+            self.occ = torch.zeros((self.K,), dtype=torch.int32, device=dev)
+            self.n = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if tuple(x_img.shape[1:]) != tuple(self.bank_img.shape[1:]) or tuple(x_tab.shape[1:]) != tuple(self.bank_tab.shape[1:]):
+            raise ValueError(f"rotta: a batch of samples {tuple(x_img.shape[1:])}, {tuple(x_tab.shape[1:])} for a bank of "
+                             f"{tuple(self.bank_img.shape[1:])}, {tuple(self.bank_tab.shape[1:])}")
+
+    @torch.no_grad()
+    def exchange(self):
+        """A <-> teacher over A's chunks, bit-exact (stil_rotta_exchange)"""
+        lib().rotta_exchange(_p(self.flat.params), _p(self.teacher), *self._slab_args(), _stream())
+
+    @torch.no_grad()
+    def move_teacher(self, nu: float):
+        """teacher <- (1 - nu) teacher + nu A over A's chunks, under the gate: a batch with n == 0 moves nothing (stil_rotta_teacher)"""
+        f = self.flat
+        lib().rotta_teacher(_p(f.params), _p(self.teacher), _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.gate),
+                            len(f.tensors), f.total, float(nu), _stream())
+
+    @torch.no_grad()
+    def bank_update(self, zt, lambda_t: float, lambda_u: float):
+        """The bank's bookkeeping moved over the batch whose teacher logits are zt [B, K] (stil_rotta_bank_update).
+        -> dict(probs, H, yhat, accepted, slot_of, counts [accepted, evictions, n after, 0], lse); writes label, unc, age, occ, n, owner"""
+        _chk(zt)
+        zt = zt.contiguous()
+        B, K = zt.shape
+        if K != self.K:
+            raise ValueError(f"rotta: logits of {K} classes for a bank of {self.K}")
+        lse, h = _empty(zt, B, torch.float64), _empty(zt, B, torch.float32)
+        yhat, slot_of = _empty(zt, B, torch.int32, 2)
+        acc = _empty(zt, B, torch.uint8)
+        p = torch.empty_like(zt)
+        counts = torch.empty((4,), dtype=torch.int32, device=zt.device)
+        lib().rotta_bank_update(_p(zt), K, B, K, self.capacity, float(lambda_t), float(lambda_u), _p(self.label), _p(self.unc), _p(self.age),
+                                _p(self.occ), _p(self.n), _p(self.owner), _p(lse), _p(p), K, _p(h), _p(yhat), _p(acc), _p(slot_of),
+                                _p(counts), _stream())
+        return dict(probs=p, H=h, yhat=yhat, accepted=acc, slot_of=slot_of, counts=counts, lse=lse)
+
+    @torch.no_grad()
+    def bank_store(self, x_img, x_tab):
+        """bank_img[s], bank_tab[s] <- the sample owner[s] of the batch, for every slot the latest bank_update handed over
+        (stil_rotta_bank_store: a bit-exact gather)"""
+        _chk(x_img, x_tab)
+        B = x_img.shape[0]
+        lib().rotta_bank_store(_p(x_img), _p(x_tab), _p(self.owner), self.capacity, B, x_img[0].numel(), x_tab[0].numel(),
+                               _p(self.bank_img), _p(self.bank_tab), _stream())
+
+
 def bn_momentum(hp, t: int) -> float:
     """alpha_t of the t-th update of the BatchNorm memory, t = 1, 2, ...: min(1, tta_bn_momentum x tta_bn_momentum_decay^t +
     tta_bn_momentum_min), DUA's schedule (Mirza et al., CVPR 2022); with the default decay 1 and minimum 0 it is tta_bn_momentum."""
@@ -881,9 +1022,11 @@ def _state(model) -> TentState:
             model._tent = CgplState(model.flat, names)
         elif model.hp.tta_method == "roid":
             model._tent = RoidState(model.flat, names, model.hp.num_classes)
+        elif model.hp.tta_method == "rotta":
+            model._tent = RottaState(model.flat, names, model.hp.num_classes, model.hp.tta_rotta_capacity)
         else:
             model._tent = TentState(model.flat, names)
-        if model.hp.tta_method == "marginal_entropy":
+        if model.hp.tta_method in ("marginal_entropy", "rotta"):
             from .augment import ImageAugmenter   # the torchvision-branch kernels: test images arrive as float CHW
             hp = model.hp
             model._tent.views = ImageAugmenter(img_size=hp.img_size, target=hp.target, kind=hp.tta_view_policy, augmentation_rate=1.0,
@@ -955,10 +1098,11 @@ def _bn_scope(model, B, update):
     return ops.bn_memory(mem, mem.alpha if N is None else B / (N + B), mem.alpha, unbiased=False, update=update)
 
 
-def _forward(model, x_img, x_tab, update=False, outputs="m"):
+def _forward(model, x_img, x_tab, update=False, outputs="m", scope=None):
     """The adapting forward -> out_m (outputs "all": the 10-tuple of forward_all, out_m first): no MI-layer dropout; BatchNorm over
-    the B images of this batch by `_bn_scope`'s rule (a short last batch gets its own rho), running buffers untouched."""
-    with ops.frozen_bn_stats(), _bn_scope(model, x_img.shape[0], update):
+    the B images of this batch by `_bn_scope`'s rule (a short last batch gets its own rho), running buffers untouched.  scope: a
+    BatchNorm rule of the caller's in place of `_bn_scope`'s (rotta_step's passes over its bank)."""
+    with ops.frozen_bn_stats(), (_bn_scope(model, x_img.shape[0], update) if scope is None else scope):
         outs = model.model.forward_all((x_img, x_tab), train=True, mi_masks=None)
         return outs if outputs == "all" else outs[0]
 
@@ -989,16 +1133,16 @@ def _grads_of(model, st):
             q.requires_grad_(f)
 
 
-def adapting_pass(model, x, st, loss_fn, update=True, outputs="m"):
+def adapting_pass(model, x, st, loss_fn, update=True, outputs="m", scope=None):
     """One adapting forward and backward on the inputs x = (images, table, ...) of a batch: the forward of `_forward`,
     loss_fn(out_m) -> (loss, probs, extras) (outputs "all": loss_fn takes the whole 10-tuple of forward_all), gradients of the
     loss for A only (no weight-gradient products) in st.grads.
     Writes st.grads and whatever loss_fn writes and, with tta_bn_momentum and `update`, the back buffer of the BatchNorm memory
-    (a constant of the backward); never a parameter, BatchNorm buffer, teacher, prototype or training slab.
+    (a constant of the backward); never a parameter, BatchNorm buffer, teacher, prototype or training slab.  scope: `_forward`'s.
     The caller holds torch.inference_mode(False).  -> (out_m, loss, probs, extras), detached."""
     x_img, x_tab = _inputs(model, x)
     with _grads_of(model, st):
-        outs = _forward(model, x_img, x_tab, update, outputs)
+        outs = _forward(model, x_img, x_tab, update, outputs, scope)
         loss, probs, extras = loss_fn(outs)
         loss.backward()
     out_m = outs[0] if outputs == "all" else outs
@@ -1079,14 +1223,15 @@ def make_views(model, x, draws=None):
     ImageAugmenter (family tta_view_policy, every row augmented, seeded by tta_view_seed when the adaptation state is created);
     the table rows repeated UNCHANGED (the model holds no table to draw corrupted cells from).  draws: the host draws of an
     earlier call (last_tta["draws"]), which rebuild its views bit for bit and leave the generator alone; None draws afresh.
+    With tta_method "rotta" x is the bank (rotta_step's strong view of it): ONE view per slot, whatever tta_views says.
     -> (views [B V, 3, P, P], table [B V, C], draws)"""
-    if model.hp.tta_method not in ("marginal_entropy", "dua"):
-        raise ValueError(f"augmented views belong to tta_method 'marginal_entropy' and 'dua' (this model: {model.hp.tta_method!r})")
+    if model.hp.tta_method not in ("marginal_entropy", "dua", "rotta"):
+        raise ValueError(f"augmented views belong to tta_method 'marginal_entropy', 'dua' and 'rotta' (this model: {model.hp.tta_method!r})")
     with torch.inference_mode(False), torch.no_grad():
         model.setup_device()
         aug = _memory(model).views if model.hp.tta_method == "dua" else _state(model).views   # dua holds no TentState
         x_img, x_tab = _inputs(model, x)
-        V = model.hp.tta_views
+        V = 1 if model.hp.tta_method == "rotta" else model.hp.tta_views
         B, _, H, W = x_img.shape
         if draws is None:
             draws = aug.draw(B * V, H, W)
@@ -1325,6 +1470,60 @@ def roid_step(model, batch):
         return model._score_test(scores, y)
 
 
+def rotta_step(model, batch):
+    """RoTTA (Yuan, Xie, Li, CVPR 2023, "Robust Test-Time Adaptation in Dynamic Scenarios"; definition as recalled: unpinned) on one
+    test batch, the method made for a temporally correlated (class-ordered) stream: the adapting pass learns from a category-balanced
+    BANK of tta_rotta_capacity test samples kept across batches on the device, not from the batch.  (1) A <-> teacher, which puts the
+    EMA teacher into A; (2) the teacher's forward on the clean batch under no_grad, the ONE forward of the batch that writes the
+    BatchNorm memory (tta_bn_momentum, RoTTA's robust BatchNorm: required): its logits give the reported scores; (3) the bank's
+    bookkeeping moves over the batch, sample by sample (stil_rotta_bank_update: a sample whose pseudo-label's class holds less than
+    its share N / K of the slots is added, or replaces the slot of highest score lambda_t / (1 + exp(-age / N)) + lambda_u unc / ln K
+    among the classes of maximal occupancy, otherwise it replaces the highest-scoring slot of its own class; in both cases only when
+    that score exceeds its own, lambda_t / 2 + lambda_u H / ln K), the accepted samples are gathered into the bank
+    (stil_rotta_bank_store) and the memory is committed; (4) the teacher's forward on all N slots of the bank under no_grad, then
+    A <-> teacher back; (5) the adapting pass on the AUGMENTED bank images (make_views: tta_view_policy, tta_view_seed, one view per
+    slot) and the unchanged table rows with rotta_loss, the timeliness-weighted cross-entropy against the teacher's logits of the
+    bank; (6) one Adam step over A if and only if the bank holds a sample; (7) teacher <- (1 - tta_rotta_nu) teacher + tta_rotta_nu A
+    under the same gate: a batch whose bank is empty moves neither A, moments, step counts nor teacher.  The step reads nothing back.
+    Unlike the published code, on purpose: (a) both passes over the bank normalise on the committed memory ALONE (rho = 0, nothing
+    written): the rows stay independent, so empty, zero-filled slots cannot leak into the filled ones, and exactly one forward of
+    the batch writes the memory -- the published robust BatchNorm updates on every forward; (b) the model adapts once per test
+    batch, the published update_frequency being tied to the batch size.
+    Writes what tent_step writes, the teacher and the bank; never the checkpoint's own EMA teacher.  The scores are the TEACHER's of
+    the clean batch, before the update; they are formed by the launch bn_adapt_step makes (softmax_rows), so tta_rotta_nu 0 with
+    tta_lr 0 reports bn_adapt's scores bit for bit.  tta_bn_prior composes in (2) as for tent_step; tta_episodic and reset_tta() empty
+    the bank and return the teacher to the source; the views' generator runs on, as marginal_entropy_step's.
+    last_tta: loss, y_hat_m (the teacher's logits of the batch), probs, probs_bank (stil_rotta_bank_update's own softmax of y_hat_m),
+    accepted, slot_of, n_bank, bank_label, bank_age (after the batch), weight [N], all on the device, and draws, the host dict
+    make_views rebuilds the views from."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False):
+        st = _begin(model)
+        mem = _memory(model)
+        x_img, x_tab = _inputs(model, x)
+        st.ensure_bank(x_img, x_tab)
+        st.exchange()
+        zt_in = _score_forward(model, x_img, x_tab, update=True)
+        probs = ops.softmax_rows(zt_in)
+        upd = st.bank_update(zt_in, hp.tta_rotta_lambda_t, hp.tta_rotta_lambda_u)
+        st.bank_store(x_img, x_tab)
+        _commit_memory(model)
+        on_memory = lambda: ops.bn_memory(mem, 0.0, mem.alpha, update=False)   # noqa: E731  the committed estimate alone, nothing written
+        with torch.no_grad():
+            zt_bank = _forward(model, st.bank_img, st.bank_tab, scope=on_memory())
+        st.exchange()
+        views, tab, draws = make_views(model, (st.bank_img, st.bank_tab))
+        _, loss, _, info = adapting_pass(model, (views, tab), st, lambda z: rotta_loss(z, zt_bank, st.label, st.age, st.active, st.gate),
+                                         update=False, scope=on_memory())
+        st.adam_step(hp.tta_lr, mask=st.gate)
+        st.move_teacher(hp.tta_rotta_nu)
+        model.last_tta = dict(loss=loss, y_hat_m=zt_in, probs=probs, probs_bank=upd["probs"], accepted=upd["accepted"],
+                              slot_of=upd["slot_of"], n_bank=upd["counts"][2], bank_label=st.label.clone(), bank_age=st.age.clone(),
+                              weight=info["w"], draws=draws)
+        return model._score_test(probs, y)
+
+
 def bn_adapt_step(model, batch):
     """"BN adapt" / "Norm", the forward-only baseline of the TTA papers: the forward of the adapting pass (BatchNorm
     statistics of this batch, blended with the source statistics under tta_bn_prior; no MI-layer dropout) and its scores.
@@ -1377,7 +1576,7 @@ def dua_step(model, batch):
 
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
          "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step,
-         "read": read_step, "cgpl": cgpl_step, "roid": roid_step}   # tta_method -> STiLModel.test_step's body
+         "read": read_step, "cgpl": cgpl_step, "roid": roid_step, "rotta": rotta_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
