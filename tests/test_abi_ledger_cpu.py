@@ -23,6 +23,8 @@ _POLICY = f"{CPU}::test_small_batch_policies_host_side"
 _INFO = f"{EP}::test_size_queries_and_library_info"
 _AUG = "test_gpu_augment.py"
 _ALB = "test_gpu_augment_alb.py"
+_AK = "test_gpu_augment_kernels.py"
+_AK_CPU = "test_augment_cases_cpu.py"
 _MATCH = "test_gpu_match.py"
 _MK = "test_gpu_match_kernels.py"
 _MK_CPU = "test_match_cases_cpu.py"
@@ -151,19 +153,30 @@ LEDGER = {
     "stil_metric_binary": [f"{EP}::test_metric_binary_at_the_threshold", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
     "stil_auroc_workspace_bytes": [f"{EP}::test_auroc_single_row_and_all_scores_equal"],
     "stil_auroc": [f"{EP}::test_auroc_single_row_and_all_scores_equal", f"{_MET}::test_multiclass_auroc", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
-    "stil_tab_corrupt": [f"{_AUG}::test_tab_corrupt_matches_reference_golden_bit_for_bit"],
+    "stil_tab_corrupt": [f"{_AUG}::test_tab_corrupt_matches_reference_golden_bit_for_bit", f"{_AK}::test_tab_corrupt_copies_and_scatters_exactly",
+                         f"{_AK_CPU}::test_tab_corrupt_refuses_before_any_launch"],
     "stil_tab_corrupt_draw": [f"{EP}::test_tab_corrupt_draw", f"{EP}::test_tab_corrupt_draw_rejects_more_than_8192_columns",
                               f"{_AUG}::test_tab_corrupt_device_draws_are_valid_and_uniform"],
-    "stil_aug_gray_mean": [f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas"],
-    "stil_aug_blur": [f"{_AUG}::test_gaussian_blur_matches_torchvision_formula"],
-    "stil_aug_rotate": [f"{_AUG}::test_rotate_matches_bilinear_reflect101_restatement"],
-    "stil_aug_hue": [f"{_AUG}::test_hue_matches_torchvision_float_formulas"],
-    "stil_aug_resize": [f"{_AUG}::test_resize_crop_flip_matches_interpolate", f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas"],
-    "stil_alb_color": [f"{_ALB}::test_color_u8_brightness_contrast_all_orders_bit_exact", f"{_ALB}::test_color_full_chain_with_hue_saturation_gray"],
-    "stil_alb_blur": [f"{_ALB}::test_blur_reflect101_borders"],
-    "stil_alb_resize": [f"{_ALB}::test_resize_crop_flip_and_to_tensor"],
-    "stil_alb_rotate": [f"{_ALB}::test_rotate_quantised_reflect101"],
-    "stil_alb_to_tensor": [f"{_ALB}::test_resize_crop_flip_and_to_tensor"],
+    "stil_aug_gray_mean": [f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas", f"{_AK}::test_gray_mean_against_float64",
+                           f"{_AK_CPU}::test_gray_mean_refuses_before_any_launch"],
+    "stil_aug_blur": [f"{_AUG}::test_gaussian_blur_matches_torchvision_formula", f"{_AK}::test_blur_against_float64",
+                      f"{_AK_CPU}::test_blur_refuses_before_any_launch"],
+    "stil_aug_rotate": [f"{_AUG}::test_rotate_matches_bilinear_reflect101_restatement", f"{_AK}::test_rotate_against_float64",
+                        f"{_AK_CPU}::test_rotate_refuses_before_any_launch"],
+    "stil_aug_hue": [f"{_AUG}::test_hue_matches_torchvision_float_formulas", f"{_AK}::test_hue_against_float64", f"{_AK_CPU}::test_hue_refuses_before_any_launch"],
+    "stil_aug_resize": [f"{_AUG}::test_resize_crop_flip_matches_interpolate", f"{_AUG}::test_colour_jitter_matches_torchvision_float_formulas",
+                        f"{_AK}::test_resize_crop_flip_against_float64", f"{_AK}::test_resize_colour_jitter_against_float64",
+                        f"{_AK}::test_resize_clamps_bad_device_boxes_into_the_image", f"{_AK_CPU}::test_resize_refuses_before_any_launch"],
+    "stil_alb_color": [f"{_ALB}::test_color_u8_brightness_contrast_all_orders_bit_exact", f"{_ALB}::test_color_full_chain_with_hue_saturation_gray",
+                       f"{_AK}::test_alb_color_at_the_pixel_count_edges_and_in_place",
+                       f"{_AK}::test_alb_color_and_to_tensor_from_a_misaligned_base_take_the_per_pixel_path",
+                       f"{_AK}::test_alb_color_with_64_workgroups_per_image"],
+    "stil_alb_blur": [f"{_ALB}::test_blur_reflect101_borders", f"{_AK}::test_alb_blur_at_the_tile_edges",
+                      f"{_AK}::test_alb_blur_on_images_shorter_than_the_radius"],
+    "stil_alb_resize": [f"{_ALB}::test_resize_crop_flip_and_to_tensor", f"{_AK}::test_alb_resize_of_one_pixel_wide_sources_both_outputs"],
+    "stil_alb_rotate": [f"{_ALB}::test_rotate_quantised_reflect101", f"{_AK}::test_alb_rotate_of_narrow_images_with_and_without_flip_first"],
+    "stil_alb_to_tensor": [f"{_ALB}::test_resize_crop_flip_and_to_tensor", f"{_AK}::test_alb_to_tensor_at_the_pixel_count_edges",
+                           f"{_AK}::test_alb_color_and_to_tensor_from_a_misaligned_base_take_the_per_pixel_path"],
     "stil_ring_enqueue": [f"{EP}::test_ring_enqueue_matches_python_ring", f"{EP}::test_ring_enqueue_rejects_bad_arguments_before_any_write"],
     "stil_queue_mean": [f"{EP}::test_queue_mean_is_colsum_bit_for_bit_and_the_float64_mean", f"{EP}::test_queue_mean_clamps_the_count"],
     "stil_rows_append": [f"{EP}::test_rows_append_matches_python_store",
