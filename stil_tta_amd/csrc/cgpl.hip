@@ -8,7 +8,7 @@
 //           of protos) -> ws and their softmax, then q, conf, mask1, the three cross-entropies and the three dZ
 //   finish  one workgroup: out, counts and the gate of the Adam step from ce3, flags and coin, in a fixed order
 // ws (doubles): the prototype logits [rows, K], only when rate < 1.
-#include "common.h"
+#include "tta_common.h"
 #include "stil_cgpl.h"
 
 struct CgplRowsArgs {
@@ -31,29 +31,6 @@ __device__ __forceinline__ int cgpl_weights(int cs, int mask1, int coin) {
   return wm | (wi << 1) | (wt << 2);
 }
 
-// largest value over the block (blockDim.x == 256); `sh` holds >= 4 doubles
-__device__ __forceinline__ double cgpl_block_max_d(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-
-// the first maximum of zr[0:K] by one 256-thread block, in every thread
-__device__ __forceinline__ int cgpl_first_max(const float* __restrict__ zr, int K, float* red, int* redi) {
-  float m = -INFINITY;
-  for (int k = threadIdx.x; k < K; k += 256) m = fmaxf(m, zr[k]);
-  m = block_max(m, red);
-  int yi = INT_MAX;
-  for (int k = threadIdx.x; k < K; k += 256)
-    if (zr[k] == m) yi = min(yi, k);
-  yi = deyo_block_min_i(yi, redi);
-  return yi >= K ? 0 : yi;  // a row without a maximum (every logit NaN): any index in range
-}
-
 // the mean of the agreeing heads' logits at column k
 __device__ __forceinline__ double cgpl_mean_logit(int cs, const float* __restrict__ zm, const float* __restrict__ zi,
                                                   const float* __restrict__ zt, int k) {
@@ -69,7 +46,7 @@ template <class At>
 __device__ __forceinline__ double cgpl_lse_d(int K, At at, double* redd) {
   double m = -INFINITY;
   for (int k = threadIdx.x; k < K; k += 256) m = fmax(m, at(k));
-  m = cgpl_block_max_d(m, redd);
+  m = block_reduce<4>(m, redd, [](double a, double b) { return fmax(a, b); });
   double s = 0.0;
   for (int k = threadIdx.x; k < K; k += 256) s += exp(at(k) - m);
   s = block_sum_d(s, redd);
@@ -87,7 +64,7 @@ __global__ __launch_bounds__(256) void cgpl_rows_kernel(CgplRowsArgs a) {
 #pragma unroll
   for (int h = 0; h < 3; ++h) {
     tta_row_lse_h(zh[h], K, red, redd, L[h], h_unused);
-    top[h] = cgpl_first_max(zh[h], K, red, redi);
+    top[h] = tta_first_max(zh[h], K, red, redi);
   }
   int cs;
   if (top[0] == top[1] && top[0] == top[2]) cs = 1;
@@ -128,7 +105,7 @@ __global__ __launch_bounds__(256) void cgpl_rows_kernel(CgplRowsArgs a) {
 #pragma unroll
     for (int h = 0; h < 3; ++h) ce[h] -= qk * ((double)zh[h][k] - L[h]);
   }
-  cmax = cgpl_block_max_d(cmax, redd);
+  cmax = block_reduce<4>(cmax, redd, [](double a, double b) { return fmax(a, b); });
 #pragma unroll
   for (int h = 0; h < 3; ++h) ce[h] = block_sum_d(ce[h], redd);
   const int mask1 = cmax >= a.th;

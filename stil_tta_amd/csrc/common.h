@@ -79,6 +79,21 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
   for (int i = 1; i < nw; ++i) r = fmaxf(r, sh[i]);
   return r;
 }
+// Block-wide reduction by an associative, commutative `op` (a minimum, a maximum) of any shuffled type, in every thread; `sh` holds
+// one entry per wave.  The combine starts from sh[0], not from a neutral element, and runs in a fixed order.  NW: the number of
+// waves where the kernel fixes it (block_reduce<4> in a kernel written for 256 threads), 0: taken from blockDim.
+template <int NW = 0, class T, class Op>
+__device__ __forceinline__ T block_reduce(T v, T* sh, Op op) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = NW ? NW : (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if (l == 0) sh[w] = v;
+  __syncthreads();
+  T r = sh[0];
+  for (int i = 1; i < nw; ++i) r = op(r, sh[i]);
+  return r;
+}
 
 // Fixed-order reduction of per-chunk partials: a block of 32*LANES threads owns 32 columns; lane l sums chunks
 // l, l+LANES, ... and the LANES lane-sums are added in order (deterministic).  part: [nplanes][nch][C].

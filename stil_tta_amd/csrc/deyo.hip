@@ -9,7 +9,7 @@
 //   Stores are fully coalesced; loads are coalesced in runs of pw floats.  In-image offsets are 32-bit (C H W < 2^31), the image
 //   base is 64-bit.
 // stil_deyo_rows, per row r of Z and Zs [rows, K]:
-//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta.hip: bit-identical)
+//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta_common.h: bit-identical)
 //   yhat_r = first maximum of Z_r ; plpd_r = p_r[yhat_r] - softmax(Zs_r)[yhat_r]
 //   rel_r = H_r < tau_Ent ; sel_r = rel_r and plpd_r > tau_PLPD ; w_r = a_ent exp(E0 - H_r) + a_plpd exp(plpd_r)
 //   n = sum sel, n_reliable = sum rel, L = (1/n) sum sel w H   (0 when n == 0)
@@ -17,10 +17,10 @@
 //   dZ_rk = sel_r w_r (-p_rk (log p_rk + H_r)) grad_scale / n  (0 when n == 0)
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
 // partials; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (tta_sel_dz_kernel of
-// csrc/tta.hip, which reads the double lse, H and w of the first back).  The loss and f = w grad_scale / n come from the code
+// csrc/tta_common.h, which reads the double lse, H and w of the first back).  The loss and f = w grad_scale / n come from the code
 // eata.hip uses (tta_sel_sums, tta_sel_dz_kernel), so that with a_ent = 1, a_plpd = 0 the results are stil_eata_rows's
 // (m invalid) bit for bit.
-#include <limits.h>
+#include "tta_common.h"
 
 template <int VEC>
 __global__ __launch_bounds__(256) void patch_shuffle_kernel(const float* __restrict__ src, float* __restrict__ dst, unsigned H,
@@ -73,17 +73,6 @@ extern "C" int stil_patch_shuffle(const float* src, float* dst, int B, int C, in
   return STIL_OK;
 }
 
-// smallest value over the block (blockDim.x == 256); `sh` holds >= 4 ints
-__device__ __forceinline__ int deyo_block_min_i(int v, int* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  return min(min(sh[0], sh[1]), min(sh[2], sh[3]));
-}
-
 __global__ __launch_bounds__(256) void deyo_rows_kernel(const float* __restrict__ Z, int ld, const float* __restrict__ Zs, int lds,
                                                          int K, double tau_ent, double tau_plpd, double e0, double a_ent,
                                                          double a_plpd, double* __restrict__ lse, double* __restrict__ Hd,
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(256) void deyo_rows_kernel(const float* __restrict_
     if (zr[k] == m) yi = min(yi, k);
     ss += exp((double)zs[k] - (double)ms);
   }
-  yi = deyo_block_min_i(yi, redi);
+  yi = block_reduce<4>(yi, redi, [](int a, int b) { return min(a, b); });
   if (yi >= K) yi = 0;  // a row without a maximum (every logit NaN): any index in range
   ss = block_sum_d(ss, redd);
   if (threadIdx.x == 0) {

@@ -2,7 +2,7 @@
 // TENT (csrc/tta.hip): a reliable / non-redundant sample selection with per-sample weights, and a Fisher-weighted anchor
 // of the adapted set A to its source values.  Per row r of Z [rows, K], with m [K] the running mean of the selected
 // predictions (valid flag *m_valid), E0 = e_margin, d = d_margin, mu = momentum:
-//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta.hip: bit-identical)
+//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta_common.h: bit-identical)
 //   c_r   = <m, p_r> / (max(|m|, 1e-8) max(|p_r|, 1e-8))     (m as it stood before the call; 0 while m is invalid)
 //   rel_r = H_r < E0 ; sel_r = rel_r and (m invalid or |c_r| < d) ; w_r = exp(E0 - H_r)
 //   n = sum sel, n_reliable = sum rel, L = (1/n) sum sel w H   (0 when n == 0)
@@ -10,10 +10,11 @@
 //   active_out[t] = active[t] and n > 0                        (the gate of the Adam step: n never leaves the device)
 //   dZ_rk = sel_r w_r (-p_rk (log p_rk + H_r)) grad_scale / n  (0 when n == 0)
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
-// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (tta_sel_dz_kernel of csrc/tta.hip, which
-// reads the double lse and H of the first back).
-// The two slab kernels visit only the 1024-float chunks of A listed in `achunks` (tta_chunk_live of csrc/tta.hip: checked
-// against chunk2tensor / active as stil_adam_step reads them); Fisher estimate and source values are compact: chunk j of them belongs to slab chunk achunks[j].
+// partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ (tta_sel_dz_kernel of
+// csrc/tta_common.h, which reads the double lse and H of the first back).
+// The two slab kernels are functors over the chunk walker of csrc/tta_common.h (TtaChunks, which states the rule for the entries of
+// `achunks`); Fisher estimate and source values are compact.
+#include "tta_common.h"
 
 __global__ __launch_bounds__(256) void eata_rows_kernel(const float* __restrict__ Z, int ld, int K, double e0, double dm,
                                                          const float* __restrict__ m, const int* __restrict__ m_valid,
@@ -116,73 +117,58 @@ extern "C" int stil_eata_rows(const float* Z, int ld, int rows, int K, float e_m
   return STIL_OK;
 }
 
-// ---- the Fisher anchor and the Fisher accumulation: one block per listed chunk
-__global__ __launch_bounds__(256) void eata_anchor_kernel(const float* __restrict__ params, const float* __restrict__ theta0,
-                                                           const float* __restrict__ fisher, float* __restrict__ grads,
-                                                           const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                           double alpha, double* __restrict__ partial) {
-  __shared__ double redd[16];
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
-    if (threadIdx.x == 0) partial[j] = 0.0;
-    return;
-  }
-  const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
-  const float4 th = reinterpret_cast<const float4*>(params)[i];
-  const float4 t0 = reinterpret_cast<const float4*>(theta0)[ic];
-  const float4 ff = reinterpret_cast<const float4*>(fisher)[ic];
-  float4 gg = reinterpret_cast<float4*>(grads)[i];
-  double s = 0.0;
+// ---- the Fisher anchor and the Fisher accumulation over A's chunks
+struct EataAnchor {  // grads += 2 alpha F (theta - theta0) -> the chunk's share of sum F (theta - theta0)^2
+  const float4* __restrict__ params; const float4* __restrict__ theta0; const float4* __restrict__ fisher;
+  float4* __restrict__ grads; double alpha;
+  __device__ double operator()(long i, long ic) const {
+    const float4 th = params[i];
+    const float4 t0 = theta0[ic];
+    const float4 ff = fisher[ic];
+    float4 gg = grads[i];
+    double s = 0.0;
 #define ANCHOR1(T, T0, F, G)                                      \
   {                                                               \
     const double d = (double)T - (double)T0, fd = (double)F * d;  \
     s += fd * d;                                                  \
     G = (float)((double)G + 2.0 * alpha * fd);                    \
   }
-  ANCHOR1(th.x, t0.x, ff.x, gg.x) ANCHOR1(th.y, t0.y, ff.y, gg.y) ANCHOR1(th.z, t0.z, ff.z, gg.z) ANCHOR1(th.w, t0.w, ff.w, gg.w)
+    ANCHOR1(th.x, t0.x, ff.x, gg.x) ANCHOR1(th.y, t0.y, ff.y, gg.y) ANCHOR1(th.z, t0.z, ff.z, gg.z) ANCHOR1(th.w, t0.w, ff.w, gg.w)
 #undef ANCHOR1
-  reinterpret_cast<float4*>(grads)[i] = gg;
-  s = block_sum_d(s, redd);
-  if (threadIdx.x == 0) partial[j] = s;
-}
+    grads[i] = gg;
+    return s;
+  }
+};
 
 __global__ __launch_bounds__(256) void eata_anchor_sum_kernel(const double* __restrict__ partial, int n, double alpha,
                                                                float* __restrict__ R) {
   __shared__ double redd[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = block_sum_d(s, redd);
+  const double s = tta_partial_sum(partial, n, redd);
   if (threadIdx.x == 0) R[0] = (float)(alpha * s);
 }
 
-__global__ __launch_bounds__(256) void eata_fisher_kernel(float* __restrict__ fisher, const float* __restrict__ grads,
-                                                           const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                           double scale) {
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
-  const float4 gg = reinterpret_cast<const float4*>(grads)[i];
-  float4 ff = reinterpret_cast<float4*>(fisher)[ic];
-  ff.x = (float)((double)ff.x + (double)gg.x * (double)gg.x * scale);
-  ff.y = (float)((double)ff.y + (double)gg.y * (double)gg.y * scale);
-  ff.z = (float)((double)ff.z + (double)gg.z * (double)gg.z * scale);
-  ff.w = (float)((double)ff.w + (double)gg.w * (double)gg.w * scale);
-  reinterpret_cast<float4*>(fisher)[ic] = ff;
-}
+struct EataFisher {  // F += g^2 scale
+  float4* __restrict__ fisher; const float4* __restrict__ grads; double scale;
+  __device__ void operator()(long i, long ic) const {
+    const float4 gg = grads[i];
+    float4 ff = fisher[ic];
+    ff.x = (float)((double)ff.x + (double)gg.x * (double)gg.x * scale);
+    ff.y = (float)((double)ff.y + (double)gg.y * (double)gg.y * scale);
+    ff.z = (float)((double)ff.z + (double)gg.z * (double)gg.z * scale);
+    ff.w = (float)((double)ff.w + (double)gg.w * (double)gg.w * scale);
+    fisher[ic] = ff;
+  }
+};
 
 extern "C" int stil_eata_anchor(const float* params, const float* theta0, const float* fisher, float* grads, const int* achunks,
                                 int n_achunks, const int* chunk2tensor, const unsigned char* active, int n_tensors, long n,
                                 float alpha, double* partial, float* R, void* stream) {
-  STIL_REQUIRE(params && theta0 && fisher && grads && achunks && chunk2tensor && active && partial && R, "stil_eata_anchor: null pointer");
-  TTA_SLAB_REQUIRE("stil_eata_anchor");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0) && ((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0),
-               "stil_eata_anchor: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_eata_anchor", c, n, {params, theta0, fisher, grads}, {partial, R})) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (n_achunks > 0) {
-    hipLaunchKernelGGL(eata_anchor_kernel, dim3(n_achunks), dim3(256), 0, s, params, theta0, fisher, grads, achunks, chunk2tensor,
-                       active, n_tensors, n / 1024, (double)alpha, partial);
+    hipLaunchKernelGGL(tta_chunk_sum_kernel<EataAnchor>, dim3(n_achunks), dim3(256), 0, s, c,
+                       EataAnchor{(const float4*)params, (const float4*)theta0, (const float4*)fisher, (float4*)grads, (double)alpha}, partial);
     STIL_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(eata_anchor_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, n_achunks, (double)alpha, R);
@@ -192,12 +178,11 @@ extern "C" int stil_eata_anchor(const float* params, const float* theta0, const 
 
 extern "C" int stil_eata_fisher_accum(float* fisher, const float* grads, const int* achunks, int n_achunks, const int* chunk2tensor,
                                       const unsigned char* active, int n_tensors, long n, float scale, void* stream) {
-  STIL_REQUIRE(fisher && grads && achunks && chunk2tensor && active, "stil_eata_fisher_accum: null pointer");
-  TTA_SLAB_REQUIRE("stil_eata_fisher_accum");
-  STIL_REQUIRE(((uintptr_t)fisher % 16 == 0) && ((uintptr_t)grads % 16 == 0), "stil_eata_fisher_accum: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_eata_fisher_accum", c, n, {fisher, grads})) return rc;
   if (n_achunks == 0) return STIL_OK;
-  hipLaunchKernelGGL(eata_fisher_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, fisher, grads, achunks, chunk2tensor,
-                     active, n_tensors, n / 1024, (double)scale);
+  hipLaunchKernelGGL(tta_chunk_kernel<EataFisher>, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, c,
+                     EataFisher{(float4*)fisher, (const float4*)grads, (double)scale});
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

@@ -8,9 +8,9 @@
 //   columns  one thread per column walks the rows in order (p recomputed from Z and the double lse; loads coalesce across
 //            columns): pbar, c -> ws, and the workgroup's partial of D -> ws
 //   dz       one workgroup per row: the row's dot product with c, then dZ (with lambda == 0: stil_entropy_rows' expression)
-//   finish   one workgroup: mean H (the sum of tta_entropy_mean_kernel) and D from the partials, in order
+//   finish   one workgroup: mean H (the sum behind stil_entropy_rows' mean) and D from the partials, in order
 // ws (doubles): c [K] | partials of D [ceil(K / 256) <= K] | H [rows]
-#include "common.h"
+#include "tta_common.h"
 
 __global__ __launch_bounds__(256) void infomax_rows_kernel(const float* __restrict__ Z, int ld, int K, double* __restrict__ lse,
                                                         float* __restrict__ p, int ldp, float* __restrict__ H,

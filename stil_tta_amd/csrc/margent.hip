@@ -10,7 +10,7 @@
 //   dz       one workgroup per row: the row's dot product with its sample's logpbar, then dZ
 //   finish   one workgroup: Hbar of every sample from its partials, in order, and their mean
 // ws (doubles): logpbar [groups, K] | partials of Hbar [groups, ceil(K / 256)]
-#include "common.h"
+#include "tta_common.h"
 
 __global__ __launch_bounds__(256) void margent_rows_kernel(const float* __restrict__ Z, int ld, int K, double* __restrict__ lse,
                                                         float* __restrict__ p, int ldp) {

@@ -10,7 +10,9 @@
 //   dz       one workgroup per row: c_r again from Z and the double lse, the row's dot product with ck, then dZ
 //   finish   infomax_finish_kernel itself over f in place of H: mean f and D from the partials, in order
 // ws (doubles): ck [K] | partials of D [ceil(K / 256) <= K]
-#include "common.h"
+// infomax_cols_kernel and infomax_finish_kernel are csrc/infomax.hip's, the one pair this file takes from a sibling rather than
+// from a header: stil_hip.hip includes infomax.hip before this file.
+#include "tta_common.h"
 #include "stil_read.h"
 
 __global__ __launch_bounds__(256) void read_rows_kernel(const float* __restrict__ Z, int ld, int K, double one_lgam,
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(256) void read_rows_kernel(const float* __restrict_
   int yi = INT_MAX;
   for (int k = threadIdx.x; k < K; k += 256)
     if (zr[k] == m) yi = min(yi, k);
-  yi = deyo_block_min_i(yi, redi);
+  yi = block_reduce<4>(yi, redi, [](int a, int b) { return min(a, b); });
   if (yi >= K) yi = 0;  // a row without a maximum (every logit NaN): any index in range
   if (threadIdx.x == 0) {
     const double lc = (double)zr[yi] - L;  // ln c_r

@@ -5,25 +5,14 @@
 // The selection couples the rows through the minimum, the maximum and the mean over the batch, hence four launches, no atomics:
 //   rows     one 256-thread workgroup per row (tta_row_lse_h: lse, p, H are stil_entropy_rows' bit for bit): the cosine with the
 //            running mean as it stands, the soft likelihood ratio; Hd, d, slr in double -> ws
-//   columns  one thread per column walks the rows in order, as infomax_cols_kernel: pbar (double) -> ws
+//   columns  one thread per column walks the rows in order, as the columns pass of csrc/infomax.hip: pbar (double) -> ws
 //   finish   one workgroup: minimum, maximum, the normalised d and c, their mean, keep, w, loss, counts; then the running mean
 //            (every cosine was read a launch ago) and the prior s -> ws
 //   dz       one workgroup per row: the row's dot product with g, then dZ; with the correction, the row's dot product with s, then scores
 // ws (doubles): Hd [rows] | d [rows] | slr [rows] | w [rows] | pbar [K] | s [K]
-#include "common.h"
-
-__device__ __forceinline__ double roid_block_min(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int i = 1; i < nw; ++i) r = fmin(r, sh[i]);
-  return r;
-}
-__device__ __forceinline__ double roid_block_max(double v, double* sh) { return -roid_block_min(-v, sh); }
+// The minima and maxima over the batch are block_reduce (csrc/common.h) with fmin, a maximum as -min(-v): what a NaN does is fmin's.
+// The ensembling is a functor over the chunk walker of csrc/tta_common.h.
+#include "tta_common.h"
 
 __global__ __launch_bounds__(256) void roid_rows_kernel(const float* __restrict__ Z, int ld, int K, const float* __restrict__ ema,
                                                          double clip, double eps, double* __restrict__ lse, float* __restrict__ p,
@@ -91,10 +80,11 @@ __global__ __launch_bounds__(256) void roid_finish_kernel(int rows, int K, doubl
     cmin = fmin(cmin, c);
     cmax = fmax(cmax, c);
   }
-  dmin = roid_block_min(dmin, redd);
-  dmax = roid_block_max(dmax, redd);
-  cmin = roid_block_min(cmin, redd);
-  cmax = roid_block_max(cmax, redd);
+  const auto least = [](double a, double b) { return fmin(a, b); };
+  dmin = block_reduce(dmin, redd, least);
+  dmax = -block_reduce(-dmax, redd, least);
+  cmin = block_reduce(cmin, redd, least);
+  cmax = -block_reduce(-cmax, redd, least);
   const double dr = dmax - dmin, cr = cmax - cmin;
   const bool ddeg = !(dr > 1e-9), cdeg = !(cr > 1e-9);  // the degenerate rule: that normalised quantity is 0 for every row
   double s = 0.0;
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(256) void roid_finish_kernel(int rows, int K, doubl
   ls = block_sum_d(ls, redd);
   double pm = 0.0;
   for (int k = threadIdx.x; k < K; k += 256) pm = fmax(pm, pbd[k]);
-  pm = roid_block_max(pm, redd);
+  pm = -block_reduce(-pm, redd, least);
   const double smooth = fmax(1.0 / (double)rows, 1.0 / (double)K) / pm;
   for (int k = threadIdx.x; k < K; k += 256) {
     const double pb = pbd[k];
@@ -213,37 +203,33 @@ extern "C" int stil_roid_rows(const float* Z, int ld, int rows, int K, float* em
   return STIL_OK;
 }
 
-// ---- weight ensembling: one block per listed chunk of A, one float4 per lane (the layout of sar_restore_kernel)
-__global__ __launch_bounds__(256) void roid_ensemble_kernel(float* __restrict__ params, const float* __restrict__ theta0,
-                                                             const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                             const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                             double m) {
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  const long i = (long)ch * 256 + threadIdx.x;
-  const float4 t0 = reinterpret_cast<const float4*>(theta0)[(long)j * 256 + threadIdx.x];
-  if (m == 0.0) {  // uniform across the grid: a copy, whatever A holds
-    reinterpret_cast<float4*>(params)[i] = t0;
-    return;
+// ---- weight ensembling over A's chunks: A <- m A + (1 - m) theta0
+struct RoidEnsemble {
+  float4* __restrict__ params; const float4* __restrict__ theta0; double m;
+  __device__ void operator()(long i, long ic) const {
+    const float4 t0 = theta0[ic];
+    if (m == 0.0) {  // uniform across the grid: a copy, whatever A holds
+      params[i] = t0;
+      return;
+    }
+    float4 th = params[i];
+    const double n1 = 1.0 - m;
+    th.x = (float)(m * (double)th.x + n1 * (double)t0.x);
+    th.y = (float)(m * (double)th.y + n1 * (double)t0.y);
+    th.z = (float)(m * (double)th.z + n1 * (double)t0.z);
+    th.w = (float)(m * (double)th.w + n1 * (double)t0.w);
+    params[i] = th;
   }
-  float4 th = reinterpret_cast<float4*>(params)[i];
-  const double n1 = 1.0 - m;
-  th.x = (float)(m * (double)th.x + n1 * (double)t0.x);
-  th.y = (float)(m * (double)th.y + n1 * (double)t0.y);
-  th.z = (float)(m * (double)th.z + n1 * (double)t0.z);
-  th.w = (float)(m * (double)th.w + n1 * (double)t0.w);
-  reinterpret_cast<float4*>(params)[i] = th;
-}
+};
 
 extern "C" int stil_roid_ensemble(float* params, const float* theta0, const int* achunks, int n_achunks, const int* chunk2tensor,
                                   const unsigned char* active, int n_tensors, long n, float momentum, void* stream) {
-  STIL_REQUIRE(params && theta0 && achunks && chunk2tensor && active, "stil_roid_ensemble: null pointer");
-  TTA_SLAB_REQUIRE("stil_roid_ensemble");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0), "stil_roid_ensemble: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_roid_ensemble", c, n, {params, theta0})) return rc;
   STIL_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "stil_roid_ensemble: momentum=%g is not inside [0, 1]", (double)momentum);
   if (n_achunks == 0 || momentum == 1.0f) return STIL_OK;
-  hipLaunchKernelGGL(roid_ensemble_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, params, theta0, achunks, chunk2tensor,
-                     active, n_tensors, n / 1024, (double)momentum);
+  hipLaunchKernelGGL(tta_chunk_kernel<RoidEnsemble>, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, c,
+                     RoidEnsemble{(float4*)params, (const float4*)theta0, (double)momentum});
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

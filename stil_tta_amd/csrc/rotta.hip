@@ -10,10 +10,11 @@
 //                flight, consecutive lanes on consecutive 16 bytes; float by float when a row is not 16-byte aligned
 //   rows         three launches as the selected-row losses: per row (both lse in double, ce, w -> ws), one workgroup (n, loss, counts,
 //                gate), per row (dZ)
-//   exchange, teacher   one block per listed chunk of A, one float4 per lane (the layout of sar_restore_kernel)
-#include "common.h"
+//   exchange, teacher   functors over the chunk walker of csrc/tta_common.h
+// The argmax stays a reduction of its own: a (score, slot) pair needs two shuffles and two LDS arrays whoever writes them, so
+// block_reduce (csrc/common.h) with a pair type would be no shorter.
+#include "tta_common.h"
 #include "stil_rotta.h"
-#include <limits.h>
 
 struct RottaBest {
   double s;
@@ -40,17 +41,6 @@ __device__ __forceinline__ RottaBest rotta_block_argmax(RottaBest v, double* shs
   __syncthreads();
   RottaBest r = {shs[0], shi[0]};
   for (int i = 1; i < nw; ++i) r = rotta_better(r, RottaBest{shs[i], shi[i]});
-  return r;
-}
-__device__ __forceinline__ int rotta_block_max_i(int v, int* shi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if (l == 0) shi[w] = v;
-  __syncthreads();
-  int r = shi[0];
-  for (int i = 1; i < nw; ++i) r = max(r, shi[i]);
   return r;
 }
 
@@ -106,7 +96,7 @@ __global__ __launch_bounds__(256) void rotta_walk_kernel(const float* __restrict
         int mo = 0;
         if (minority) {
           for (int k = tid; k < K; k += 256) mo = max(mo, occ[k]);
-          mo = rotta_block_max_i(mo, shi);
+          mo = block_reduce(mo, shi, [](int a, int b) { return max(a, b); });
         }
         RottaBest best = {-INFINITY, INT_MAX};
         for (int i = tid; i < n; i += 256) {
@@ -349,56 +339,50 @@ extern "C" int stil_rotta_rows(const float* Zs, int lds, const float* Zt, int ld
   return STIL_OK;
 }
 
-// ---- the teacher over A: one block per listed chunk, one float4 per lane
-__global__ __launch_bounds__(256) void rotta_exchange_kernel(float* __restrict__ params, float* __restrict__ teacher,
-                                                              const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                              const unsigned char* __restrict__ active, int n_tensors, long nchunks) {
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  const long i = (long)ch * 256 + threadIdx.x, jt = (long)j * 256 + threadIdx.x;
-  const float4 a = reinterpret_cast<float4*>(params)[i];
-  const float4 t = reinterpret_cast<float4*>(teacher)[jt];
-  reinterpret_cast<float4*>(params)[i] = t;
-  reinterpret_cast<float4*>(teacher)[jt] = a;
-}
+// ---- the teacher over A's chunks
+struct RottaExchange {  // A <-> teacher
+  float4* __restrict__ params; float4* __restrict__ teacher;
+  __device__ void operator()(long i, long ic) const {
+    const float4 a = params[i];
+    const float4 t = teacher[ic];
+    params[i] = t;
+    teacher[ic] = a;
+  }
+};
 
-__global__ __launch_bounds__(256) void rotta_teacher_kernel(const float* __restrict__ params, float* __restrict__ teacher,
-                                                             const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                             const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                             double nu) {
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  const float4 a = reinterpret_cast<const float4*>(params)[(long)ch * 256 + threadIdx.x];
-  float4 t = reinterpret_cast<float4*>(teacher)[(long)j * 256 + threadIdx.x];
-  const double n1 = 1.0 - nu;
-  t.x = (float)(n1 * (double)t.x + nu * (double)a.x);
-  t.y = (float)(n1 * (double)t.y + nu * (double)a.y);
-  t.z = (float)(n1 * (double)t.z + nu * (double)a.z);
-  t.w = (float)(n1 * (double)t.w + nu * (double)a.w);
-  reinterpret_cast<float4*>(teacher)[(long)j * 256 + threadIdx.x] = t;
-}
+struct RottaTeacher {  // teacher <- (1 - nu) teacher + nu A
+  const float4* __restrict__ params; float4* __restrict__ teacher; double nu;
+  __device__ void operator()(long i, long ic) const {
+    const float4 a = params[i];
+    float4 t = teacher[ic];
+    const double n1 = 1.0 - nu;
+    t.x = (float)(n1 * (double)t.x + nu * (double)a.x);
+    t.y = (float)(n1 * (double)t.y + nu * (double)a.y);
+    t.z = (float)(n1 * (double)t.z + nu * (double)a.z);
+    t.w = (float)(n1 * (double)t.w + nu * (double)a.w);
+    teacher[ic] = t;
+  }
+};
 
 extern "C" int stil_rotta_exchange(float* params, float* teacher, const int* achunks, int n_achunks, const int* chunk2tensor,
                                    const unsigned char* active, int n_tensors, long n, void* stream) {
-  STIL_REQUIRE(params && teacher && achunks && chunk2tensor && active, "stil_rotta_exchange: null pointer");
-  TTA_SLAB_REQUIRE("stil_rotta_exchange");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)teacher % 16 == 0), "stil_rotta_exchange: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_rotta_exchange", c, n, {params, teacher})) return rc;
   if (n_achunks == 0) return STIL_OK;
-  hipLaunchKernelGGL(rotta_exchange_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, params, teacher, achunks, chunk2tensor,
-                     active, n_tensors, n / 1024);
+  hipLaunchKernelGGL(tta_chunk_kernel<RottaExchange>, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, c,
+                     RottaExchange{(float4*)params, (float4*)teacher});
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
 
 extern "C" int stil_rotta_teacher(const float* params, float* teacher, const int* achunks, int n_achunks, const int* chunk2tensor,
                                   const unsigned char* active, int n_tensors, long n, float nu, void* stream) {
-  STIL_REQUIRE(params && teacher && achunks && chunk2tensor && active, "stil_rotta_teacher: null pointer");
-  TTA_SLAB_REQUIRE("stil_rotta_teacher");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)teacher % 16 == 0), "stil_rotta_teacher: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_rotta_teacher", c, n, {params, teacher})) return rc;
   STIL_REQUIRE(nu >= 0.0f && nu <= 1.0f, "stil_rotta_teacher: nu=%g is not inside [0, 1]", (double)nu);
   if (n_achunks == 0 || nu == 0.0f) return STIL_OK;
-  hipLaunchKernelGGL(rotta_teacher_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, params, teacher, achunks, chunk2tensor,
-                     active, n_tensors, n / 1024, (double)nu);
+  hipLaunchKernelGGL(tta_chunk_kernel<RottaTeacher>, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, c,
+                     RottaTeacher{(const float4*)params, (float4*)teacher, (double)nu});
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

@@ -2,17 +2,18 @@
 // TENT (csrc/tta.hip) and beside EATA (csrc/eata.hip): the entropy of the reliable rows, minimised at the adversarially
 // perturbed point theta + rho g / |g|, and a model-recovery rule on a running mean of the loss.  Per row r of Z [rows, K],
 // with E0 = margin and prior_r the selection of an earlier pass (all ones when there is none):
-//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta.hip: bit-identical)
+//   lse_r, p_rk, H_r                as stil_entropy_rows (tta_row_lse_h of csrc/tta_common.h: bit-identical)
 //   sel_r = prior_r and H_r < E0 ; n = sum sel ; L = (1/n) sum sel H   (0 when n == 0; no weights)
 //   active_out[t] = active[t] and n > 0                        (the gate of the Adam step: n never leaves the device)
 //   dZ_rk = sel_r (-p_rk (log p_rk + H_r)) grad_scale / n      (0 when n == 0)
 //   second pass: ema <- L | mu ema + (1 - mu) L when n > 0 ; recover = reset > 0 and ema held and ema < reset
 // Everything is formed in double and rounded once; reductions are wave64 shuffle trees plus a fixed-order sum of the wave
 // partials or fixed-order loops; no float atomics: bit-identical on repetition.  Three launches: rows, reduce, dZ
-// (tta_sel_dz_kernel of csrc/tta.hip with weight 1, which reads the double lse and H of the first back).
-// The slab kernels visit only the 1024-float chunks of A listed in `achunks` (tta_chunk_live of csrc/tta.hip: checked
-// against chunk2tensor / active as stil_adam_step reads them); saved values, the perturbation and the source values are
-// compact: chunk j of them belongs to slab chunk achunks[j].  What one block hands to another crosses a launch boundary.
+// (tta_sel_dz_kernel of csrc/tta_common.h with weight 1, which reads the double lse and H of the first back).
+// The slab kernels walk A's chunks as csrc/tta_common.h lays down (TtaChunks, which states the rule for the entries of `achunks`):
+// the square norm and the restore are functors over its kernel templates, perturb and recover are kernels of their own on its
+// helper.  Saved values, the perturbation and the source values are compact.  What one block hands to another crosses a launch boundary.
+#include "tta_common.h"
 
 __global__ __launch_bounds__(256) void sar_rows_kernel(const float* __restrict__ Z, int ld, int K, double e0,
                                                         const unsigned char* __restrict__ prior, double* __restrict__ lse,
@@ -102,41 +103,26 @@ extern "C" int stil_sar_rows(const float* Z, int ld, int rows, int K, float marg
   return STIL_OK;
 }
 
-// ---- the slab kernels: one block per listed chunk, one float4 per lane
-__global__ __launch_bounds__(256) void sar_sqnorm_kernel(const float* __restrict__ grads, const int* __restrict__ achunks,
-                                                          const int* __restrict__ chunk2tensor,
-                                                          const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                          double* __restrict__ partial) {
-  __shared__ double redd[16];
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) {  // uniform across the block
-    if (threadIdx.x == 0) partial[j] = 0.0;
-    return;
+// ---- the slab kernels
+struct SarSqnorm {  // the chunk's share of |g|^2
+  const float4* __restrict__ grads;
+  __device__ double operator()(long i, long) const {
+    const float4 g = grads[i];
+    return (double)g.x * (double)g.x + (double)g.y * (double)g.y + (double)g.z * (double)g.z + (double)g.w * (double)g.w;
   }
-  const float4 g = reinterpret_cast<const float4*>(grads)[(long)ch * 256 + threadIdx.x];
-  double s = (double)g.x * (double)g.x + (double)g.y * (double)g.y + (double)g.z * (double)g.z + (double)g.w * (double)g.w;
-  s = block_sum_d(s, redd);
-  if (threadIdx.x == 0) partial[j] = s;
-}
+};
 
 // every block sums the partials itself, in the same fixed order: the norm is one value for all of them
-__global__ __launch_bounds__(256) void sar_perturb_kernel(float* __restrict__ params, const float* __restrict__ grads,
-                                                           float* __restrict__ saved, float* __restrict__ e,
-                                                           const int* __restrict__ achunks, int n_achunks,
-                                                           const int* __restrict__ chunk2tensor,
-                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                           double rho, const double* __restrict__ partial,
-                                                           double* __restrict__ norm) {
+__global__ __launch_bounds__(256) void sar_perturb_kernel(TtaChunks c, float* __restrict__ params, const float* __restrict__ grads,
+                                                           float* __restrict__ saved, float* __restrict__ e, double rho,
+                                                           const double* __restrict__ partial, double* __restrict__ norm) {
   __shared__ double redd[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n_achunks; i += 256) s += partial[i];
-  s = block_sum_d(s, redd);
-  const double nrm = sqrt(s);
-  const int j = blockIdx.x, ch = achunks[j];
+  const double nrm = sqrt(tta_partial_sum(partial, c.n_achunks, redd));
+  const int j = blockIdx.x;
   if (j == 0 && threadIdx.x == 0) norm[0] = nrm;
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
+  long i, ic;
+  if (!c.at(j, i, ic)) return;
   const double f = rho / (nrm + 1e-12);
-  const long i = (long)ch * 256 + threadIdx.x, ic = (long)j * 256 + threadIdx.x;
   const float4 g = reinterpret_cast<const float4*>(grads)[i];
   float4 th = reinterpret_cast<float4*>(params)[i];
   reinterpret_cast<float4*>(saved)[ic] = th;
@@ -157,34 +143,28 @@ __global__ void sar_zero_norm_kernel(double* __restrict__ norm) {  // an empty A
   if (threadIdx.x == 0) norm[0] = 0.0;
 }
 
-__global__ __launch_bounds__(256) void sar_restore_kernel(float* __restrict__ params, const float* __restrict__ saved,
-                                                           const int* __restrict__ achunks, const int* __restrict__ chunk2tensor,
-                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks) {
-  const int j = blockIdx.x, ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  reinterpret_cast<float4*>(params)[(long)ch * 256 + threadIdx.x] = reinterpret_cast<const float4*>(saved)[(long)j * 256 + threadIdx.x];
-}
+struct SarRestore {  // A <- saved
+  float4* __restrict__ params; const float4* __restrict__ saved;
+  __device__ void operator()(long i, long ic) const { params[i] = saved[ic]; }
+};
 
 // grid = n_achunks + 1: the last block clears the step counts and the validity of the running mean
-__global__ __launch_bounds__(256) void sar_recover_kernel(float* __restrict__ params, const float* __restrict__ theta0,
+__global__ __launch_bounds__(256) void sar_recover_kernel(TtaChunks c, float* __restrict__ params, const float* __restrict__ theta0,
                                                            float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                                           int* __restrict__ steps, const int* __restrict__ achunks, int n_achunks,
-                                                           const int* __restrict__ chunk2tensor,
-                                                           const unsigned char* __restrict__ active, int n_tensors, long nchunks,
-                                                           const int* __restrict__ recover, int* __restrict__ ema_valid) {
+                                                           int* __restrict__ steps, const int* __restrict__ recover,
+                                                           int* __restrict__ ema_valid) {
   if (recover[0] == 0) return;  // uniform across the grid
   const int j = blockIdx.x;
-  if (j == n_achunks) {
-    for (int t = threadIdx.x; t < n_tensors; t += 256)
-      if (active[t]) steps[t] = 0;
+  if (j == c.n_achunks) {
+    for (int t = threadIdx.x; t < c.n_tensors; t += 256)
+      if (c.active[t]) steps[t] = 0;
     if (threadIdx.x == 0) ema_valid[0] = 0;
     return;
   }
-  const int ch = achunks[j];
-  if (!tta_chunk_live(ch, nchunks, chunk2tensor, active, n_tensors)) return;
-  const long i = (long)ch * 256 + threadIdx.x;
+  long i, ic;
+  if (!c.at(j, i, ic)) return;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  reinterpret_cast<float4*>(params)[i] = reinterpret_cast<const float4*>(theta0)[(long)j * 256 + threadIdx.x];
+  reinterpret_cast<float4*>(params)[i] = reinterpret_cast<const float4*>(theta0)[ic];
   reinterpret_cast<float4*>(exp_avg)[i] = zero;
   reinterpret_cast<float4*>(exp_avg_sq)[i] = zero;
 }
@@ -192,33 +172,29 @@ __global__ __launch_bounds__(256) void sar_recover_kernel(float* __restrict__ pa
 extern "C" int stil_sar_perturb(float* params, const float* grads, float* saved, float* e, const int* achunks, int n_achunks,
                                 const int* chunk2tensor, const unsigned char* active, int n_tensors, long n, float rho, double* partial,
                                 double* norm, void* stream) {
-  STIL_REQUIRE(params && grads && saved && e && achunks && chunk2tensor && active && partial && norm, "stil_sar_perturb: null pointer");
-  TTA_SLAB_REQUIRE("stil_sar_perturb");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_sar_perturb", c, n, {params, grads, saved, e}, {partial, norm})) return rc;
   STIL_REQUIRE(rho >= 0.f && rho <= 3.0e38f, "stil_sar_perturb: rho=%g must be a finite number >= 0", (double)rho);
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)grads % 16 == 0) && ((uintptr_t)saved % 16 == 0) && ((uintptr_t)e % 16 == 0),
-               "stil_sar_perturb: slabs must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   if (n_achunks == 0) {
     hipLaunchKernelGGL(sar_zero_norm_kernel, dim3(1), dim3(64), 0, s, norm);
     STIL_LAUNCH_CHECK();
     return STIL_OK;
   }
-  hipLaunchKernelGGL(sar_sqnorm_kernel, dim3(n_achunks), dim3(256), 0, s, grads, achunks, chunk2tensor, active, n_tensors, n / 1024, partial);
+  hipLaunchKernelGGL(tta_chunk_sum_kernel<SarSqnorm>, dim3(n_achunks), dim3(256), 0, s, c, SarSqnorm{(const float4*)grads}, partial);
   STIL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sar_perturb_kernel, dim3(n_achunks), dim3(256), 0, s, params, grads, saved, e, achunks, n_achunks, chunk2tensor, active,
-                     n_tensors, n / 1024, (double)rho, (const double*)partial, norm);
+  hipLaunchKernelGGL(sar_perturb_kernel, dim3(n_achunks), dim3(256), 0, s, c, params, grads, saved, e, (double)rho, (const double*)partial, norm);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
 
 extern "C" int stil_sar_restore(float* params, const float* saved, const int* achunks, int n_achunks, const int* chunk2tensor,
                                 const unsigned char* active, int n_tensors, long n, void* stream) {
-  STIL_REQUIRE(params && saved && achunks && chunk2tensor && active, "stil_sar_restore: null pointer");
-  TTA_SLAB_REQUIRE("stil_sar_restore");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)saved % 16 == 0), "stil_sar_restore: slabs must be 16-byte aligned");
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_sar_restore", c, n, {params, saved})) return rc;
   if (n_achunks == 0) return STIL_OK;
-  hipLaunchKernelGGL(sar_restore_kernel, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, params, saved, achunks, chunk2tensor, active,
-                     n_tensors, n / 1024);
+  hipLaunchKernelGGL(tta_chunk_kernel<SarRestore>, dim3(n_achunks), dim3(256), 0, (hipStream_t)stream, c,
+                     SarRestore{(float4*)params, (const float4*)saved});
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }
@@ -226,13 +202,10 @@ extern "C" int stil_sar_restore(float* params, const float* saved, const int* ac
 extern "C" int stil_sar_recover(float* params, const float* theta0, float* exp_avg, float* exp_avg_sq, int* steps, const int* achunks,
                                 int n_achunks, const int* chunk2tensor, const unsigned char* active, int n_tensors, long n,
                                 const int* recover, int* ema_valid, void* stream) {
-  STIL_REQUIRE(params && theta0 && exp_avg && exp_avg_sq && steps && achunks && chunk2tensor && active && recover && ema_valid,
-               "stil_sar_recover: null pointer");
-  TTA_SLAB_REQUIRE("stil_sar_recover");
-  STIL_REQUIRE(((uintptr_t)params % 16 == 0) && ((uintptr_t)theta0 % 16 == 0) && ((uintptr_t)exp_avg % 16 == 0) && ((uintptr_t)exp_avg_sq % 16 == 0),
-               "stil_sar_recover: slabs must be 16-byte aligned");
-  hipLaunchKernelGGL(sar_recover_kernel, dim3(n_achunks + 1), dim3(256), 0, (hipStream_t)stream, params, theta0, exp_avg, exp_avg_sq, steps,
-                     achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024, recover, ema_valid);
+  const TtaChunks c = {achunks, n_achunks, chunk2tensor, active, n_tensors, n / 1024};
+  if (int rc = tta_slab_check("stil_sar_recover", c, n, {params, theta0, exp_avg, exp_avg_sq}, {steps, recover, ema_valid})) return rc;
+  hipLaunchKernelGGL(sar_recover_kernel, dim3(n_achunks + 1), dim3(256), 0, (hipStream_t)stream, c, params, theta0, exp_avg, exp_avg_sq, steps,
+                     recover, ema_valid);
   STIL_LAUNCH_CHECK();
   return STIL_OK;
 }

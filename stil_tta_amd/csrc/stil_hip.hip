@@ -30,6 +30,8 @@ extern "C" int stil_device_count(void) {
 #include "augment_alb.hip"
 #include "layout.hip"
 #include "state.hip"
+// the adaptation files share through tta_common.h, which each includes itself: their order is free, but for read.hip, which
+// launches two kernels of infomax.hip and so comes after it
 #include "tta.hip"
 #include "eata.hip"
 #include "infomax.hip"

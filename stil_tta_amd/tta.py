@@ -648,10 +648,11 @@ class CompactState(TentState):
     def _compact_views(self, buf):
         return [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._spans, self.tensors)]
 
-    def _slab_args(self):
-        """what every slab entry point takes to find A's chunks: achunks, n_achunks, chunk2tensor, active, n_tensors, n"""
+    def _slab_args(self, mask=None):
+        """what every slab entry point takes to find A's chunks: achunks, n_achunks, chunk2tensor, active, n_tensors, n
+        (`mask`: a per-tensor mask to walk under in place of `active`)"""
         f = self.flat
-        return _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.active), len(f.tensors), f.total
+        return _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.active if mask is None else mask), len(f.tensors), f.total
 
     @torch.no_grad()
     def snapshot(self):
@@ -884,9 +885,7 @@ class RottaState(CompactState):
     @torch.no_grad()
     def move_teacher(self, nu: float):
         """teacher <- (1 - nu) teacher + nu A over A's chunks, under the gate: a batch with n == 0 moves nothing (stil_rotta_teacher)"""
-        f = self.flat
-        lib().rotta_teacher(_p(f.params), _p(self.teacher), _p(self.achunks), self.n_achunks, _p(f.chunk2tensor), _p(self.gate),
-                            len(f.tensors), f.total, float(nu), _stream())
+        lib().rotta_teacher(_p(self.flat.params), _p(self.teacher), *self._slab_args(mask=self.gate), float(nu), _stream())
 
     @torch.no_grad()
     def bank_update(self, zt, lambda_t: float, lambda_u: float):
