@@ -366,11 +366,19 @@ int stil_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 /* ---- evaluation metrics (torchmetrics==0.11.0 as used by STiLModel.py:122-145, 360-363, 458-463, 529-545) ----
  * hits_total: device int64[2] = {hits, samples}, accumulated (integer atomics: order-independent).
  * metric_topk: target class within the k best scores of its row (k = 1: argmax's first-maximum rule); k > K is accepted and
- *        counts what k = K counts (every row whose target is a valid class).
- * metric_binary: (prob > threshold) == (target == 1).
+ *        counts what k = K counts (every row whose target is a valid class).  The rank is the target's position in
+ *        torch.sort(row, descending=True, stable=True): among equal scores (+0.0 == -0.0) the lower index is first, and a
+ *        NaN ranks above every number as in ATen's argmax / topk -- a row of NaNs is a hit for target 0 only, a NaN
+ *        anywhere in a row takes the first place from every number.  A target outside [0, K) is a sample, never a hit.
+ * metric_binary: (prob > threshold) == (target == 1); a NaN prob predicts 0, a target other than 1 is "not 1".
  * auroc: exact area under the ROC curve (thresholds=None); K == 1: binary on scores[:,0] with positives target == 1;
  *        K > 1: one-vs-rest per class and their unweighted mean (macro; a class without positives or negatives
- *        scores 0).  Integer rank statistics per class (segmented radix sort), no float accumulation. */
+ *        scores 0; a target outside [0, K) is a negative of every class).  Integer rank statistics per class (segmented
+ *        radix sort), no float accumulation: auc[c] = (float)(U2 / (2.0 * n_pos * n_neg)) in float64, macro = (float) of the
+ *        float64 sum of auc[] in class order over K.  Scores may be any non-NaN float (signed, +-0.0 equal, +-inf,
+ *        subnormal).  NaN scores are OUT OF CONTRACT: the call returns and writes only its outputs, the classes whose own
+ *        column holds no NaN keep their exact values, a class with a NaN in its column gets an unspecified number.
+ *        N >= 1, K >= 1, ld >= K, N * K < 2^31; ws_bytes >= stil_auroc_workspace_bytes(N, K) (0 for a shape it refuses). */
 int stil_metric_topk(const float* scores, int ld, const long long* target, int N, int K, int k,
                      long long* hits_total, void* stream);
 int stil_metric_binary(const float* probs, const long long* target, int N, float threshold, long long* hits_total,

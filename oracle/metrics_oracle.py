@@ -13,11 +13,12 @@ import numpy as np
 
 
 def topk_accuracy(preds: np.ndarray, target: np.ndarray, k: int = 1) -> float:
-    """ties resolved towards the lower class index (argmax's first-maximum rule for k = 1)."""
+    """ties resolved towards the lower class index (argmax's first-maximum rule for k = 1); a NaN ranks above every number, as
+    ATen's argmax / topk take it: a NaN score beats the target unless the target is a NaN at a lower index."""
     n, K = preds.shape
     st = preds[np.arange(n), target][:, None]
-    idx = np.arange(K)[None, :]
-    beat = ((preds > st) | ((preds == st) & (idx < target[:, None]))).sum(1)
+    lower = np.arange(K)[None, :] < target[:, None]
+    beat = np.where(np.isnan(preds), ~np.isnan(st) | lower, (preds > st) | ((preds == st) & lower)).sum(1)
     return float((beat < k).mean())
 
 

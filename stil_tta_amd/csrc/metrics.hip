@@ -9,7 +9,9 @@
 
 // ---------------------------------------------------------------------------------------------- accuracy counters
 // one wave per row: the target class is "in the top k" when fewer than k scores beat it (ties resolved towards the lower
-// index, so k = 1 is exactly argmax's first-maximum rule).
+// index, so k = 1 is exactly argmax's first-maximum rule).  A NaN ranks above every number, as in ATen's argmax / topk / sort:
+// a NaN score beats the target unless the target is itself a NaN at a lower (or the same) index, and a NaN target is beaten by
+// nothing else -- the row's position in torch.sort(descending=True, stable=True).  A row of NaNs is a hit for target 0 only.
 __global__ __launch_bounds__(256) void topk_hits_kernel(const float* __restrict__ s, int ld, const long long* __restrict__ y,
                                                          int N, int K, int k, unsigned long long* __restrict__ cnt) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -22,7 +24,7 @@ __global__ __launch_bounds__(256) void topk_hits_kernel(const float* __restrict_
     int beat = 0;
     for (int j = lane; j < K; j += 64) {
       const float v = r[j];
-      beat += (v > st) || (v == st && j < t);
+      beat += (v != v) ? (st == st || j < t) : ((v > st) || (v == st && j < t));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) beat += __shfl_xor(beat, o, 64);
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void binary_hits_kernel(const float* __restric
 
 extern "C" int stil_metric_topk(const float* scores, int ld, const long long* target, int N, int K, int k,
                                 long long* hits_total, void* stream) {
-  STIL_REQUIRE(N >= 0 && K >= 1 && k >= 1 && ld >= K, "metric_topk: bad shape N=%d K=%d k=%d ld=%d", N, K, k, ld);
+  STIL_REQUIRE(N >= 0 && K >= 1 && k >= 1 && ld >= K, "stil_metric_topk: bad shape N=%d K=%d k=%d ld=%d", N, K, k, ld);
   if (N == 0) return STIL_OK;
   hipLaunchKernelGGL(topk_hits_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, scores, ld, target, N, K, k,
                      (unsigned long long*)hits_total);
@@ -62,7 +64,7 @@ extern "C" int stil_metric_topk(const float* scores, int ld, const long long* ta
 
 extern "C" int stil_metric_binary(const float* probs, const long long* target, int N, float threshold, long long* hits_total,
                                   void* stream) {
-  STIL_REQUIRE(N >= 0, "metric_binary: bad N=%d", N);
+  STIL_REQUIRE(N >= 0, "stil_metric_binary: bad N=%d", N);
   if (N == 0) return STIL_OK;
   hipLaunchKernelGGL(binary_hits_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, probs, target, N, threshold,
                      (unsigned long long*)hits_total);
@@ -194,10 +196,10 @@ __global__ void auroc_macro_kernel(const float* __restrict__ auc, int K, float* 
 
 extern "C" int stil_auroc(const float* scores, int ld, const long long* target, int N, int K, float* auc_per_class, float* macro,
                           void* ws, size_t ws_bytes, void* stream) {
-  STIL_REQUIRE(N >= 1 && K >= 1 && ld >= K, "auroc: bad shape N=%d K=%d ld=%d", N, K, ld);
-  STIL_REQUIRE((long)N * K < (1L << 31), "auroc: N*K = %ld exceeds the 2^31 element limit of the segmented sort", (long)N * K);
+  STIL_REQUIRE(N >= 1 && K >= 1 && ld >= K, "stil_auroc: bad shape N=%d K=%d ld=%d", N, K, ld);
+  STIL_REQUIRE((long)N * K < (1L << 31), "stil_auroc: N*K = %ld exceeds the 2^31 element limit of the segmented sort", (long)N * K);
   AurocWs w = auroc_layout(ws, N, K);
-  STIL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "auroc: workspace %zu < %zu bytes", ws_bytes, w.total);
+  STIL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "stil_auroc: workspace %zu < %zu bytes", ws_bytes, w.total);
   hipStream_t st = (hipStream_t)stream;
   const long KN = (long)K * N;
   hipLaunchKernelGGL(auroc_scatter_kernel, dim3(cdiv(KN + 1, 256)), dim3(256), 0, st, scores, ld, target, N, K, K == 1 ? 1 : 0, w.kin,
@@ -207,7 +209,7 @@ extern "C" int stil_auroc(const float* scores, int ld, const long long* target, 
   hipError_t e = hipcub::DeviceSegmentedRadixSort::SortPairs(w.cub, cb, (const float*)w.kin, w.kout, (const unsigned char*)w.fin, w.fout,
                                                              (int)KN, K, (const int*)w.offs, (const int*)w.offs + 1, 0, 32, st);
   if (e != hipSuccess) {
-    stil_set_error("auroc: segmented sort failed: %s", hipGetErrorString(e));
+    stil_set_error("stil_auroc: segmented sort failed: %s", hipGetErrorString(e));
     return STIL_EHIP;
   }
   hipLaunchKernelGGL(auroc_scan_kernel, dim3(K), dim3(1024), 0, st, (const unsigned char*)w.fout, N, w.negpre);

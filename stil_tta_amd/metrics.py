@@ -3,8 +3,9 @@
 
 Accuracy keeps two int64 counters on the device (hits, samples); AUROC keeps the epoch's scores and computes the exact
 (thresholds=None) area with integer rank statistics in `stil_auroc`.  Under data parallelism `.compute()` reduces the
-counters / gathers the scores over the process group (torchmetrics' sync-on-compute).  No host sync until `.compute()`
-is read.  There is no CPU path: the kernels live in libstil_hip.so.
+counters / gathers the scores over the process group (torchmetrics' sync-on-compute); it reaches the collectives before it
+decides anything, so a rank that received no rows takes part and an error is raised on every rank or on none.  Scores are
+converted with `.to(float32)`, targets with `.to(int64)`.  No host sync until `.compute()` is read.  There is no CPU path: the kernels live in libstil_hip.so.
 """
 from __future__ import annotations
 
@@ -19,6 +20,11 @@ from .ops import _p, _stream, _ws
 
 def _dist_on() -> bool:
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
+def _here() -> torch.device:
+    """the device of a rank that holds no tensor yet"""
+    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _prep(preds: torch.Tensor, target: torch.Tensor):
@@ -51,11 +57,13 @@ class Accuracy:
     __call__ = update
 
     def compute(self) -> torch.Tensor:
-        if self.counts is None:
-            raise RuntimeError("Accuracy.compute() before any update")
-        c = self.counts.clone()
-        if _dist_on():
+        if _dist_on():   # the collective first: a rank that saw no batch joins with zero counters (its peers are waiting in all_reduce)
+            c = torch.zeros(2, dtype=torch.int64, device=_here()) if self.counts is None else self.counts.clone()
             dist.all_reduce(c, op=dist.ReduceOp.SUM)
+        elif self.counts is None:
+            raise RuntimeError("Accuracy.compute() before any update")
+        else:
+            c = self.counts
         return c[0].to(torch.float32) / c[1].to(torch.float32)
 
     def reset(self) -> None:
@@ -67,6 +75,9 @@ class Accuracy:
         if self.counts is None and device is not None:
             self.counts = torch.zeros(2, dtype=torch.int64, device=device)
         return [] if self.counts is None else [self.counts]
+
+
+_NO_ROWS = "AUROC.compute(): no rows arrived since the last reset() (no update, or only zero-row updates)"
 
 
 class AUROC:
@@ -126,36 +137,57 @@ class AUROC:
     __call__ = update
 
     def _local(self):
+        """-> (scores [n, K], targets [n], error or None) of this rank; n = 0 (and K = 0 where the width is not known yet) on a
+        rank nothing arrived at.  An overflowed reservation is reported, not raised: compute() raises after the collectives."""
         if self.store is None:
-            return torch.cat(self.preds), torch.cat(self.target)
+            if self.preds:
+                return torch.cat(self.preds), torch.cat(self.target), None
+            if not _dist_on():
+                raise RuntimeError(_NO_ROWS)
+            K = 1 if self.task == "binary" else int(self.num_classes or 0)
+            return torch.empty((0, K), dtype=torch.float32, device=_here()), torch.empty((0,), dtype=torch.int64, device=_here()), None
         sc, st, cnt, ovf = self.store
         n, full = int(cnt.item()), int(ovf.item())
         if full or n > sc.shape[0]:
-            raise RuntimeError(f"AUROC: {n} rows arrived for a reservation of {sc.shape[0]} (AUROC.reserve)")
-        return sc[:n], st[:n]
+            return sc[:0], st[:0], f"AUROC: {n} rows arrived for a reservation of {sc.shape[0]} (AUROC.reserve)"
+        return sc[:n], st[:n], None
 
     def _gathered(self):
-        p, y = self._local()
+        """Every rank's rows in rank order.  The first collective carries (rows, columns, overflowed) of each rank, so a rank
+        without rows takes part like any other, learns the width from its peers, and every rank sees the same global state
+        before anything is raised."""
+        p, y, err = self._local()
         if not _dist_on():
+            if err:
+                raise RuntimeError(err)
             return p, y
-        n = torch.tensor([p.shape[0]], dtype=torch.int64, device=p.device)
-        sizes = [torch.zeros_like(n) for _ in range(dist.get_world_size())]
-        dist.all_gather(sizes, n)
-        nmax = int(max(int(s) for s in sizes))
-        pp = torch.zeros((nmax, p.shape[1]), dtype=p.dtype, device=p.device)
+        head = torch.tensor([p.shape[0], p.shape[1], 1 if err else 0], dtype=torch.int64, device=p.device)
+        heads = [torch.zeros_like(head) for _ in range(dist.get_world_size())]
+        dist.all_gather(heads, head)
+        heads = [[int(v) for v in h.tolist()] for h in heads]
+        if any(h[2] for h in heads):
+            raise RuntimeError(err or f"AUROC: the reservation of rank {[h[2] for h in heads].index(1)} overflowed (AUROC.reserve)")
+        sizes, K = [h[0] for h in heads], max(h[1] for h in heads)
+        if any(h[0] and h[1] != K for h in heads):
+            raise RuntimeError(f"AUROC: the ranks hold scores of different widths {[h[1] for h in heads]}")
+        nmax = max(sizes)
+        if nmax == 0:
+            return p.new_empty((0, K)), y
+        pp = torch.zeros((nmax, K), dtype=p.dtype, device=p.device)
         yy = torch.zeros((nmax,), dtype=y.dtype, device=p.device)
-        pp[: p.shape[0]], yy[: y.shape[0]] = p, y
+        if p.shape[0]:
+            pp[: p.shape[0]], yy[: y.shape[0]] = p, y
         ps = [torch.empty_like(pp) for _ in sizes]
         ys = [torch.empty_like(yy) for _ in sizes]
         dist.all_gather(ps, pp)
         dist.all_gather(ys, yy)
-        return (torch.cat([t[: int(s)] for t, s in zip(ps, sizes)]), torch.cat([t[: int(s)] for t, s in zip(ys, sizes)]))
+        return torch.cat([t[:n] for t, n in zip(ps, sizes)]), torch.cat([t[:n] for t, n in zip(ys, sizes)])
 
     def compute(self) -> torch.Tensor:
-        if not self.has_updates():
-            raise RuntimeError("AUROC.compute() before any update")
-        p, y = self._gathered()
+        p, y = self._gathered()   # before any decision: under data parallelism every rank has to reach the collectives
         N, K = p.shape
+        if N == 0:
+            raise RuntimeError(_NO_ROWS)
         nb = lib().auroc_workspace_bytes(N, K)
         if nb == 0:
             raise RuntimeError(f"AUROC: {N} x {K} scores exceed the 2^31-element limit")

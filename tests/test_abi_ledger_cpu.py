@@ -29,6 +29,8 @@ _MATCH = "test_gpu_match.py"
 _MK = "test_gpu_match_kernels.py"
 _MK_CPU = "test_match_cases_cpu.py"
 _MET = "test_gpu_metrics.py"
+_METK = "test_gpu_metric_kernels.py"
+_METK_CPU = "test_metric_cases_cpu.py"
 _ATT = "test_gpu_attention.py"
 _ATT_CPU = "test_attention_config_cpu.py"
 KE = "test_gpu_kernel_edges.py"
@@ -149,10 +151,18 @@ LEDGER = {
     "stil_ema_update": [f"{OPS}::test_ema_and_adam_slabs", f"{KE}::test_ema_update_is_bit_exact_past_the_grid_cap", f"{KE}::test_ema_update_on_a_sub_slab"],
     "stil_ema_int_trunc": [f"{EP}::test_ema_int_trunc"],
     "stil_adam_step": [f"{OPS}::test_ema_and_adam_slabs", f"{KE}::test_adam_five_steps_with_padding_and_a_lagging_tensor", f"{KE}::test_adam_slab_beyond_the_grid_cap"],
-    "stil_metric_topk": [f"{EP}::test_metric_topk_on_a_column_slice_and_k_edges", f"{_MET}::test_topk_accuracy_counts"],
-    "stil_metric_binary": [f"{EP}::test_metric_binary_at_the_threshold", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
-    "stil_auroc_workspace_bytes": [f"{EP}::test_auroc_single_row_and_all_scores_equal"],
-    "stil_auroc": [f"{EP}::test_auroc_single_row_and_all_scores_equal", f"{_MET}::test_multiclass_auroc", f"{_MET}::test_binary_accuracy_and_auroc_with_ties"],
+    "stil_metric_topk": [f"{EP}::test_metric_topk_on_a_column_slice_and_k_edges", f"{_MET}::test_topk_accuracy_counts",
+                         f"{_METK}::test_topk_counters_equal_the_sorted_position", f"{_METK}::test_topk_nan_rows_one_by_one",
+                         f"{_METK}::test_counters_add_over_calls_and_an_empty_call_leaves_them",
+                         f"{_METK_CPU}::test_top1_reference_is_atens_argmax_nan_rows_included"],
+    "stil_metric_binary": [f"{EP}::test_metric_binary_at_the_threshold", f"{_MET}::test_binary_accuracy_and_auroc_with_ties",
+                           f"{_METK}::test_binary_counters_equal_the_comparison", f"{_METK}::test_counters_add_over_calls_and_an_empty_call_leaves_them",
+                           f"{_METK_CPU}::test_binary_reference_is_atens_comparison"],
+    "stil_auroc_workspace_bytes": [f"{EP}::test_auroc_single_row_and_all_scores_equal", f"{_METK}::test_auroc_workspace_bound_and_refusals"],
+    "stil_auroc": [f"{EP}::test_auroc_single_row_and_all_scores_equal", f"{_MET}::test_multiclass_auroc", f"{_MET}::test_binary_accuracy_and_auroc_with_ties",
+                   f"{_METK}::test_auroc_equals_the_pair_count_bit_for_bit", f"{_METK}::test_auroc_workspace_bound_and_refusals",
+                   f"{_METK}::test_auroc_nan_in_one_column_leaves_the_other_classes_alone",
+                   f"{_METK}::test_two_rank_metrics_equal_one_process_on_the_concatenation", f"{_METK_CPU}::test_auroc_reference_against_sklearn"],
     "stil_tab_corrupt": [f"{_AUG}::test_tab_corrupt_matches_reference_golden_bit_for_bit", f"{_AK}::test_tab_corrupt_copies_and_scatters_exactly",
                          f"{_AK_CPU}::test_tab_corrupt_refuses_before_any_launch"],
     "stil_tab_corrupt_draw": [f"{EP}::test_tab_corrupt_draw", f"{EP}::test_tab_corrupt_draw_rejects_more_than_8192_columns",

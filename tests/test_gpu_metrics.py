@@ -1,10 +1,23 @@
 """Device metrics (stil_tta_amd/metrics.py, csrc/metrics.hip) against oracle/metrics_oracle.py: counters are exact, the
-AUROC is integer rank statistics on the same fp32 scores -> equal to the oracle to the final float division."""
+AUROC is integer rank statistics on the same fp32 scores -> the oracle's float64 value rounded once to fp32, bit for bit
+(tests/test_gpu_metric_kernels.py holds the kernels at their edges against a pair-counting reference)."""
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _macro32(per):
+    """auroc_macro_kernel: the float64 sum of the fp32 per-class values in class order, over K, rounded once"""
+    total = 0.0
+    for v in per:
+        total += _f32(v)
+    return _f32(total / len(per))
 
 
 def _softmax(z):
@@ -25,7 +38,7 @@ def test_topk_accuracy_counts(N, K, k):
     m(torch.from_numpy(z[half:]).cuda(), torch.from_numpy(y[half:]).cuda())
     assert int(m.counts[1]) == N
     assert int(m.counts[0]) == round(MO.topk_accuracy(z, y, k) * N)
-    assert abs(float(m.compute()) - MO.topk_accuracy(z, y, k)) < 1e-6
+    assert abs(float(m.compute()) - MO.topk_accuracy(z, y, k)) < 1e-6       # one fp32 division of the exact counters above
     m.reset()
     assert int(m.counts.sum()) == 0
 
@@ -42,8 +55,9 @@ def test_binary_accuracy_and_auroc_with_ties():
         for a, b in ((0, N // 3), (N // 3, N)):
             acc(torch.from_numpy(s[a:b]).cuda(), torch.from_numpy(y[a:b]).cuda())
             auc(torch.from_numpy(s[a:b]).cuda(), torch.from_numpy(y[a:b]).cuda())
-        assert abs(float(acc.compute()) - MO.binary_accuracy(s, y)) < 1e-6
-        assert abs(float(auc.compute()) - MO.binary_auroc(s, y == 1)) < 1e-6
+        assert int(acc.counts[0]) == round(MO.binary_accuracy(s, y) * N) and int(acc.counts[1]) == N
+        assert abs(float(acc.compute()) - MO.binary_accuracy(s, y)) < 1e-6   # one fp32 division of the exact counters above
+        assert float(auc.compute()) == _f32(MO.binary_auroc(s, y == 1))
 
 
 @pytest.mark.parametrize("N,K", [(50, 3), (777, 13), (4096, 286), (20000, 286)])
@@ -61,8 +75,8 @@ def test_multiclass_auroc(N, K):
         m(torch.from_numpy(p[a:a + step]).cuda(), torch.from_numpy(y[a:a + step]).cuda())
     got = float(m.compute())
     macro, per = MO.multiclass_auroc(p, y)
-    assert np.abs(m.per_class.cpu().numpy().astype(np.float64) - per).max() < 1e-6
-    assert abs(got - macro) < 1e-6
+    assert np.array_equal(m.per_class.cpu().numpy(), per.astype(np.float32))
+    assert got == _macro32(per) and abs(got - macro) < 1e-6
 
 
 def test_metric_errors():
@@ -102,7 +116,7 @@ def test_model_eval_hooks_track_oracle_metrics():
     m.validation_epoch_end()
     out = m.test_epoch_end()
     assert abs(float(out["test.acc"]) - MO.topk_accuracy(P, Y, 1)) < 1e-6
-    assert abs(float(out["test.auc"]) - MO.multiclass_auroc(P, Y)[0]) < 1e-6
+    assert float(out["test.auc"]) == _macro32(MO.multiclass_auroc(P, Y)[1])
     assert abs(float(m.logged["eval.val.acc"]) - MO.topk_accuracy(P, Y, 1)) < 1e-6
     assert abs(m.best_val_score - MO.topk_accuracy(P, Y, 1)) < 1e-6
     assert int(m.acc_val.counts.sum()) == 0
