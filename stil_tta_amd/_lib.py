@@ -1,5 +1,5 @@
 """ctypes binding of libstil_hip.so, generated from include/stil_hip.h, the test-time adaptation headers (TTA_HEADERS) and the
-headers kept beside their kernels (MEMORY_HEADERS, READ_HEADERS, CGPL_HEADERS, SHIFT_HEADERS, ROID_HEADERS, ROTTA_HEADERS) at import time.
+headers kept beside their kernels (MEMORY_HEADERS, READ_HEADERS, CGPL_HEADERS, SHIFT_HEADERS, ROID_HEADERS, ROTTA_HEADERS, LAME_HEADERS) at import time.
 
 There is NO fallback: if the shared library is missing, or a call returns an error, a
 RuntimeError is raised (the product path must never silently run on something else).
@@ -28,6 +28,8 @@ SHIFT_HEADERS = (os.path.join(_HERE, "csrc", "stil_shift.h"),)
 ROID_HEADERS = (os.path.join(_HERE, "csrc", "stil_roid.h"),)
 # RoTTA's sample bank, its loss and the teacher over A (csrc/rotta.hip), likewise: tests/test_rotta_abi_ledger_cpu.py holds its ledger
 ROTTA_HEADERS = (os.path.join(_HERE, "csrc", "stil_rotta.h"),)
+# LAME's neighbour affinity and its iterated label correction (csrc/lame.hip), likewise: tests/test_lame_abi_ledger_cpu.py holds its ledger
+LAME_HEADERS = (os.path.join(_HERE, "csrc", "stil_lame.h"),)
 LIB_PATH = os.environ.get("STIL_LIB_PATH") or os.path.join(_HERE, "lib", "libstil_hip.so")  # STIL_LIB_PATH: A/B builds of the same sources (tests/tools)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -100,7 +102,7 @@ class _Lib:
                                f"(or `make -C {CSRC}`) first; there is no fallback path")
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
-        for header in TTA_HEADERS + MEMORY_HEADERS + READ_HEADERS + CGPL_HEADERS + SHIFT_HEADERS + ROID_HEADERS + ROTTA_HEADERS:
+        for header in TTA_HEADERS + MEMORY_HEADERS + READ_HEADERS + CGPL_HEADERS + SHIFT_HEADERS + ROID_HEADERS + ROTTA_HEADERS + LAME_HEADERS:
             self.protos.update(parse_header(header))
         for name, (restype, argl) in self.protos.items():
             fn = getattr(self._dll, name)  # AttributeError if the header declares a symbol the .so lacks

@@ -42,4 +42,5 @@ extern "C" int stil_device_count(void) {
 #include "cgpl.hip"
 #include "roid.hip"
 #include "rotta.hip"
+#include "lame.hip"
 #include "shift.hip"

@@ -52,6 +52,7 @@ _DEFAULTS = dict(
                          # | "cgpl" (STiL's own consensus pseudo-labels over out_m, out_i, out_t on the test batch; below)
                          # | "roid" (Marsden et al., WACV 2024: soft likelihood ratio, weight ensembling with the source, prior correction; below)
                          # | "rotta" (Yuan et al., CVPR 2023: a device-side bank of test samples and an EMA teacher, for class-ordered streams; needs tta_bn_momentum; below)
+                         # | "lame" (Boudiaf et al., CVPR 2022: forward only, the batch's probabilities corrected along a neighbour graph of the features, the model untouched; below)
                          # | "deyo" | "sar" (below) | "dua" (Mirza et al., CVPR 2022: forward only, augmented views move a running estimate of the BatchNorm statistics; needs tta_bn_momentum)
     tta_lr=1e-3,         # TENT's Adam: betas (0.9, 0.999), eps 1e-8, no weight decay
     tta_episodic=False,  # True: restore the adapted parameters and clear their moments before every batch
@@ -112,6 +113,14 @@ _DEFAULTS = dict(
     tta_rotta_nu=0.001,               # in [0, 1]: the teacher moves this share of the way to the student after every step
     tta_rotta_lambda_t=1.0,           # >= 0: weight of a slot's age in its eviction score
     tta_rotta_lambda_u=1.0,           # >= 0: weight of a slot's uncertainty (the entropy of the teacher's prediction over ln K) in it
+    # "lame" only: LAME (Boudiaf et al., CVPR 2022), forward only: the model stays at the source and the batch's probabilities are pulled together
+    # along a k-nearest-neighbour graph of the multimodal classifier's input.  tta_bn_prior / tta_bn_momentum switch the forward to bn_adapt's.
+    # Definition and defaults as recalled from the paper and its published code: unpinned
+    tta_lame_affinity="knn",          # "knn": a neighbour weighs 1 | "rbf": exp(-d2 / (2 s2)), s2 the mean distance to the k-th neighbour
+    tta_lame_knn=5,                   # k >= 1: neighbours per row (at most the batch's other rows)
+    tta_lame_lambda=1.0,              # >= 0: weight of the neighbours' predictions in a row's update; 0: the scores stay softmax(out_m)
+    tta_lame_steps=100,               # >= 1: the most fixed-point steps a batch runs
+    tta_lame_tol=1e-8,                # >= 0: stop when the energy moves by no more than this relatively (from step 2 on); 0: always tta_lame_steps steps
 )
 
 
@@ -707,6 +716,8 @@ class STiLModel(_Base):
         corrected by the batch's prior (tta_roid_prior_correction), before the update.
         With "rotta" (tta.rotta_step) an EMA teacher of A scores the batch (the reported scores) and decides which samples enter a
         category-balanced bank kept on the device across batches; the model then adapts on the augmented bank against the teacher.
+        With "lame" (tta.lame_step) nothing of the model moves: this very forward (bn_adapt's under tta_bn_prior / tta_bn_momentum) is
+        followed by a correction of the batch's probabilities along a nearest-neighbour graph of the multimodal classifier's input.
         With tta_bn_momentum every method but "read" normalises on that estimate (tta.BnMemory) instead of the checkpoint's statistics."""
         if self._tta_on():
             return tta.STEPS[self.hp.tta_method](self, batch)

@@ -28,6 +28,10 @@ Every method but SAR and READ is ONE adapting pass (`adapting_pass`) with its ow
                            teacher's logits of the bank -> Adam over A gated by n > 0 -> the teacher moves tta_rotta_nu towards A
     estimate_fisher        argmax_ce         -> fisher += g^2 / N
     bn_adapt_step          the pass's forward alone under no_grad, softmax_rows: no state, no gradient
+    lame_step              LAME (Boudiaf et al., CVPR 2022; as recalled: unpinned): test_step's own forward in eval mode (with tta_bn_prior
+                           or tta_bn_momentum: bn_adapt_step's), then lame_correct on the logits and the multimodal classifier's input:
+                           the batch's probabilities are pulled together along a k-nearest-neighbour graph of the features (`lame_correct`);
+                           the one method that touches only the outputs: no state, no gradient, nothing of the model moves
     dua_step               encoder_imaging alone on V views of every sample under no_grad, which moves the BatchNorm memory by alpha_t
                            (DUA, Mirza et al., CVPR 2022) -> the clean batch scored in eval mode on the memory: no gradient
 With tta_bn_momentum every forward above normalises on the BatchNorm memory (`BnMemory`, model._bn_mem: a running estimate of the
@@ -55,6 +59,8 @@ from .ops import _chk, _p, _scale_by, _stream, join_side
 PARAMS = ("bn", "norm", "fusion")
 VIEW_POLICIES = ("contrastive", "hard_eval", "soft_eval", "weak", "strong")   # augment._policy's transform families
 ROTTA_MAX_SLOTS = 4096   # STIL_ROTTA_MAX_SLOTS of csrc/stil_rotta.h: the one workgroup that walks the samples bounds the bank
+LAME_MAX_ROWS = 2048     # STIL_LAME_MAX_ROWS of csrc/stil_lame.h: a row's distances are ranked in the LDS of its workgroup
+LAME_AFFINITIES = ("knn", "rbf")   # STIL_LAME_KNN, STIL_LAME_RBF: the index is the kind stil_lame_affinity takes
 
 
 def _number(hp, key, lo=None, strict=False, also=()):
@@ -133,6 +139,12 @@ def check_hparams(hp):
         raise ValueError(f"tta_rotta_nu must not exceed 1, not {hp.tta_rotta_nu!r}")
     if hp.tta_rotta_capacity > ROTTA_MAX_SLOTS:
         raise ValueError(f"tta_rotta_capacity must not exceed {ROTTA_MAX_SLOTS}, the bound of stil_rotta_bank_update, not {hp.tta_rotta_capacity!r}")
+    if not isinstance(hp.tta_lame_affinity, str) or hp.tta_lame_affinity not in LAME_AFFINITIES:
+        raise ValueError(f"Unknown tta_lame_affinity {hp.tta_lame_affinity!r}: valid are {LAME_AFFINITIES}")
+    _int_from(hp, "tta_lame_knn", 1)
+    _number(hp, "tta_lame_lambda", 0)
+    _int_from(hp, "tta_lame_steps", 1)
+    _number(hp, "tta_lame_tol", 0)
     if hp.tta_method == "read" and hp.tta_params != "fusion":
         raise ValueError(f"tta_method 'read' adapts the fusion attention alone: set tta_params 'fusion' (this model: {hp.tta_params!r})")
     if hp.tta_params == "fusion" and hp.tta_method != "read":
@@ -521,6 +533,46 @@ def rotta_loss(z, zt, label, age, active=None, gate=None):
         return loss, None, dz
 
     return _RowLossFn.apply(z.contiguous(), launch) + (info,)
+
+
+def lame_correct(z, feats, k=5, kind="knn", lam=1.0, max_steps=100, tol=1e-8):
+    """LAME's correction (Boudiaf, Mueller, Ben Ayed, Bertinetto, CVPR 2022, "Parameter-free Online Test-time Adaptation"; definition
+    and defaults as recalled from the paper and its published code: unpinned) of the logits z [rows, K] of one batch along the
+    features feats [rows, D]; no autograd, nothing of the model is read.  With fhat the normalised features and d2 = 2 - 2 <fhat_i,
+    fhat_j>, every row gets its k' = min(k, rows - 1) nearest other rows (ties to the lower index, a NaN distance last), weighted 1
+    ("knn") or exp(-d2 / (2 s2)) ("rbf", s2 the mean distance to the k'-th neighbour); A = (W + W^T) / 2; then from
+    u = log(softmax(z) + 1e-10) and Y^0 = softmax(u) the Jacobi iteration Y^n_i = softmax(u_i + lam sum_j A_ij Y^(n-1)_j) runs until
+    its energy moves by no more than tol relatively (after step 2 at the earliest; tol 0: never) or max_steps steps are done.  The
+    stopping rule is decided on the device: all 3 + 2 + max_steps + 1 launches of stil_lame_affinity and stil_lame_rows (csrc/stil_lame.h
+    states the arithmetic) are enqueued, those after the rule has fired return at once, nothing is read back.
+    Unlike the published code, on purpose: all in double; the energy uses A Y^(n-1), what the update read; this project's tie and NaN
+    rules; no "linear" affinity.
+    -> (Y [rows, K] the corrected scores, p = softmax(z) in stil_entropy_rows' bits, info); info = dict(nbr [rows, k] int32 (-1: padding),
+    wts [rows, k], dk [rows] float64, steps [1] int32, energy [max_steps] float64 (NaN from `steps` on), lse [rows] float64)."""
+    z, feats = z.detach().contiguous(), feats.detach().contiguous()
+    _chk(z, feats)
+    if z.dim() != 2 or feats.dim() != 2 or feats.shape[0] != z.shape[0] or z.dtype != torch.float32 or feats.dtype != torch.float32:
+        raise ValueError(f"lame_correct: float32 logits [rows, K] and features [rows, D], not {tuple(z.shape)} {z.dtype} and {tuple(feats.shape)} {feats.dtype}")
+    R, K = z.shape
+    D = feats.shape[1]
+    if R > LAME_MAX_ROWS:
+        raise ValueError(f"lame_correct: a batch of {R} rows exceeds LAME_MAX_ROWS = {LAME_MAX_ROWS}, the bound of stil_lame_affinity")
+    if kind not in LAME_AFFINITIES:
+        raise ValueError(f"lame_correct: unknown affinity {kind!r}: valid are {LAME_AFFINITIES}")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1 or isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 1:
+        raise ValueError(f"lame_correct: k and max_steps must be ints >= 1, not {k!r} and {max_steps!r}")
+    dev = z.device
+    nbr = torch.empty((R, k), dtype=torch.int32, device=dev)
+    wts = torch.empty((R, k), dtype=torch.float32, device=dev)
+    dk, lse = _empty(z, R, torch.float64, 2)
+    ws = _empty(z, max(R * (1 + min(k, R)), 2 * R * R + 3 * R * K + 3 * R + 2), torch.float64)   # the two calls are ordered: one scratch
+    lib().lame_affinity(_p(feats), D, R, D, k, LAME_AFFINITIES.index(kind), _p(nbr), _p(wts), _p(dk), _p(ws), _stream())
+    p, Y = torch.empty_like(z), torch.empty_like(z)
+    energy = torch.full((max_steps,), float("nan"), dtype=torch.float64, device=dev)
+    steps = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib().lame_rows(_p(z), K, R, K, _p(nbr), _p(wts), k, float(lam), max_steps, float(tol), _p(lse), _p(p), K, _p(Y), K, _p(energy),
+                    _p(steps), _p(ws), _stream())
+    return Y, p, dict(nbr=nbr, wts=wts, dk=dk, steps=steps, energy=energy, lse=lse)
 
 
 def marginal_entropy(z, groups, views, want_probs=False):
@@ -1106,11 +1158,11 @@ def _forward(model, x_img, x_tab, update=False, outputs="m", scope=None):
         return outs if outputs == "all" else outs[0]
 
 
-def _score_forward(model, x_img, x_tab, update=False):
-    """The forward of `_forward` alone, under no_grad on the layouts of the current weights -> out_m"""
+def _score_forward(model, x_img, x_tab, update=False, outputs="m"):
+    """The forward of `_forward` alone, under no_grad on the layouts of the current weights -> out_m (outputs "all": the 10-tuple)"""
     with torch.no_grad():
         model.flat.refresh_layouts(student=True, teacher=False)
-        return _forward(model, x_img, x_tab, update)
+        return _forward(model, x_img, x_tab, update, outputs)
 
 
 @contextlib.contextmanager
@@ -1540,6 +1592,43 @@ def bn_adapt_step(model, batch):
         return model._score_test(probs, y)
 
 
+def lame_step(model, batch):
+    """LAME (Boudiaf, Mueller, Ben Ayed, Bertinetto, CVPR 2022, "Parameter-free Online Test-time Adaptation"; definition and defaults
+    as recalled from the paper and its published code: unpinned) on one test batch, the forward-only method made for the streams on
+    which adapting the model degrades (class-ordered, label-shifted; batches of two or three classes): the model and its
+    normalisation stay at the source, the batch's output probabilities are corrected (`lame_correct`: tta_lame_knn neighbours per row
+    under tta_lame_affinity, tta_lame_lambda, at most tta_lame_steps steps, tta_lame_tol).
+    The forward: with tta_bn_prior and tta_bn_momentum both None it is the plain test_step's (eval mode, the checkpoint's statistics,
+    forward_all(..., train=False)); with either set it is bn_adapt_step's (`_score_forward` with the update, then the memory's
+    commit): the paper's "LAME on adapted statistics".  The features are the multimodal classifier's own input, cat(e_si, e_c, e_st).
+    No TentState, no adapted set, no optimiser, no gradient: reset_tta() and tta_episodic act on the BatchNorm memory only, as for
+    bn_adapt_step.  The step reads nothing back; a batch above LAME_MAX_ROWS rows is refused before its forward.
+    Not part of this method: the "linear" affinity, LAME stacked on a method that adapts parameters, neighbours across batches.
+    last_tta: y_hat_m, probs (Y, the reported scores), probs_raw (softmax(y_hat_m) by the launch test_step and bn_adapt_step make, so
+    bit for bit theirs; lame_correct's own p, stil_entropy_rows' bits, differs from it in the last place), features, neighbours
+    [B, tta_lame_knn] (-1: padding), steps [1], energy [tta_lame_steps] (NaN from `steps` on), all on the device."""
+    x, y = batch
+    hp = model.hp
+    with torch.inference_mode(False), torch.no_grad():
+        model.setup_device()
+        x_img, x_tab = _inputs(model, x)
+        if x_img.shape[0] > LAME_MAX_ROWS:
+            raise ValueError(f"tta_method 'lame': a batch of {x_img.shape[0]} rows exceeds LAME_MAX_ROWS = {LAME_MAX_ROWS}")
+        if hp.tta_bn_prior is None and hp.tta_bn_momentum is None:
+            outs = model.model.forward_all((x_img, x_tab), train=False)
+        else:
+            _begin_memory(model)
+            outs = _score_forward(model, x_img, x_tab, update=True, outputs="all")
+            _commit_memory(model)
+        out_m = outs[0].detach().contiguous()
+        feats = torch.cat([outs[3], outs[9], outs[6]], dim=1)
+        probs_raw = ops.softmax_rows(out_m)
+        Y, _, info = lame_correct(out_m, feats, hp.tta_lame_knn, hp.tta_lame_affinity, hp.tta_lame_lambda, hp.tta_lame_steps, hp.tta_lame_tol)
+        model.last_tta = dict(y_hat_m=out_m, probs=Y, probs_raw=probs_raw, features=feats, neighbours=info["nbr"], steps=info["steps"],
+                              energy=info["energy"])
+        return model._score_test(Y, y)
+
+
 def dua_step(model, batch):
     """DUA (Mirza et al., CVPR 2022, "The norm must go on") on one test batch of B samples, B = 1 being the case it is made for.
     Forward only: no adapted set, no gradient, no optimiser, no TentState; the BatchNorm memory (BnMemory) is all that adapts.
@@ -1575,7 +1664,7 @@ def dua_step(model, batch):
 
 STEPS = {"tent": tent_step, "eata": eata_step, "bn_adapt": bn_adapt_step, "shot_im": shot_im_step,
          "marginal_entropy": marginal_entropy_step, "deyo": deyo_step, "sar": sar_step, "dua": dua_step,
-         "read": read_step, "cgpl": cgpl_step, "roid": roid_step, "rotta": rotta_step}   # tta_method -> STiLModel.test_step's body
+         "read": read_step, "cgpl": cgpl_step, "roid": roid_step, "rotta": rotta_step, "lame": lame_step}   # tta_method -> STiLModel.test_step's body
 METHODS = (None,) + tuple(STEPS)
 
 
